@@ -1,6 +1,8 @@
 """bench.py -- headline benchmark of the ControlLoRA hot path on MI355X (contract in the task brief).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py --gpus N --steps K --warmup W --full   (plus every secondary measurement, see below)
+  python bench.py ... --dump-outputs DIR                 (plus what the last timed step computed, as DIR/<name>.npy)
 
 One "step" = one full training step of the hot path on a synthetic fill50k-like batch resident in HBM:
 hint-encoder forward, SD-1.5 UNet forward with the 32 ControlLoRA processors, fp32 MSE, backward (dgrad
@@ -13,10 +15,13 @@ outside the named hot path: latents and text embeddings a
 ranks (one per GPU, RCCL); launched BY `torch.distributed.run` (the driver's way) it just joins.  `n_gpus` in the
 line is the number of ranks that actually joined (`torch.distributed.get_world_size()`).
 
-Prints ONE JSON line (rank 0) with metric/value plus `roofline` (dominant kernel family: algorithmic flops of its
-launches in one step / its kernel time per GRAPH-REPLAYED step, taken from a `rocprofv3 --kernel-trace` of this same
-command run as a child process; HIP-event timings of an eager step are reported beside it) and `cpu_baseline` (the
-CPU oracle, N=1 only).
+A plain run sets up, runs W warm-up steps, times exactly K steps in one window, writes its outputs if asked to, and prints
+ONE JSON line (rank 0) with metric/value/ms_per_step.  `--full` adds what the headline does not need: the box calibration,
+three timed windows of K steps (the line then reports the median window), the exchange-step timing, the DDIM and
+whole-reference-step lines, `roofline` (dominant kernel family: algorithmic flops of its launches in one step / its
+kernel time per GRAPH-REPLAYED step, taken from a `rocprofv3 --kernel-trace` of this same command run as a child process;
+HIP-event timings of an eager step are reported beside it) and `cpu_baseline` (the CPU oracle, N=1 only).  Keys of the
+line whose measurement did not run are null.
 """
 from __future__ import annotations
 
@@ -346,6 +351,43 @@ def dry_run(args):
     return 0 if ok else 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write each tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy: float64 tensors stay float64, everything else becomes
+    float32.  When the whole set would exceed `limit` bytes, the largest arrays are replaced by a fixed seeded sample of their
+    flattened elements (the same indices for every array of one size, sorted), so that two runs stay comparable element by
+    element.  Returns {name: {"shape", "dtype", "sampled"}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+    sizes = {k: v.numel() * v.element_size() for k, v in host.items()}
+    keep = {}
+    budget, left = limit, sorted(host, key=lambda k: sizes[k])
+    while left:                                  # smallest first: each array gets at most an equal share of what remains
+        name = left.pop(0)
+        share = budget // (len(left) + 1)
+        v = host[name]
+        if sizes[name] > share:
+            k = share // v.element_size()
+            if k == 0:
+                raise ValueError(f"--dump-outputs: no room left for {name!r} under {limit} bytes")
+            g = torch.Generator().manual_seed(seed)
+            idx = torch.randperm(v.numel(), generator=g)[:k].sort().values
+            v = v.reshape(-1)[idx]
+            keep[name] = {"shape": list(host[name].shape), "sampled": k}
+        else:
+            keep[name] = {"shape": list(v.shape), "sampled": None}
+        keep[name]["dtype"] = str(v.dtype).replace("torch.", "")
+        budget -= v.numel() * v.element_size()
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.numpy())
+    return keep
+
+
 GEMM_FAMILY = ("gemm_dma_kernel", "conv3x3_patch_kernel", "splitk_finish_kernel", "gemm_")       # kernels behind clora_gemm_f16_ex
 
 
@@ -469,7 +511,13 @@ def main():
                          '"clora" = the C ABI\'s own RCCL communicator (clora_comm_init / clora_allreduce_flat_f32); same '
                          'ncclAllReduce either way; "auto" (default) = clora when world > 1 on an nccl group, a requested clora that '
                          'cannot be set up falls back to torch with a warning and `comm_fallback` in the line (also: CLORA_COMM)')
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each; the line reports the median window")
+    ap.add_argument("--full", action="store_true", help="also run every secondary measurement: box calibration, three timed windows, "
+                    "exchange-step timing, DDIM and whole-reference-step lines, roofline (rocprofv3 child runs), CPU oracle baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last timed step computed "
+                    "(UNet prediction, loss, updated adapter parameters, their gradients) as DIR/<name>.npy, at most 64 MB in all; that step starts "
+                    "from the state as set up (restored inside the last window), so its inputs are the same in every run")
+    ap.add_argument("--windows", type=int, default=None, help="timed windows of --steps steps each; the line reports the median window "
+                    "(default 1, with --full 3)")
     ap.add_argument("--no-calibration", action="store_true", help="skip the box calibration (8192^3 GEMM, 256 MB copy, MFMA clock probe)")
     ap.add_argument("--dry-run", action="store_true", help="with --backend gloo: exercise the multi-rank control flow (spawn, "
                     "rendezvous, flat all-reduce, rank-0 line) without touching a GPU")
@@ -485,6 +533,10 @@ def main():
         sys.exit(spawn_ranks(args.gpus))
     if args.dry_run:
         sys.exit(dry_run(args))
+    if args.windows is None:
+        args.windows = 3 if args.full else 1
+    if not args.full:                          # a plain run: set-up, warm-up, the timed steps, outputs, the line
+        args.no_cpu_baseline = args.no_roofline = args.no_ddim = args.no_full_step = args.no_calibration = True
     if args.trace_child:
         args.no_cpu_baseline = args.no_roofline = args.no_ddim = args.no_full_step = True
         args.windows = 1                       # the parent divides the child's launch counts by 2 + warmup + steps
@@ -511,11 +563,20 @@ def main():
 
     unet, clora = build_models(dev, config=args.config)
     trainer = ControlLoRATrainer(unet, clora, process_group=pg, world_size=world, comm=args.comm)   # falls back loudly (comm_fallback)
+    # --dump-outputs: the last timed step starts from the trainer state as set up here (seeded weights, zero moments), restored inside
+    # the last window (a device copy of the flat buffers + one operand repack launch).  Its inputs -- batch and state -- are then the
+    # same in every run: the training trajectory before it would carry the rounding differences of the float atomics (loss sum,
+    # gradient sums) into the weights and grow them step by step (UNet prediction 2e-3 apart after 27 steps, 6e-2 after 112)
+    start_state = None
+    if args.dump_outputs:
+        start_state = {"params": trainer.flat.data.clone(), "exp_avg": trainer.flat.exp_avg.clone(),
+                       "exp_avg_sq": trainer.flat.exp_avg_sq.clone(), "state": trainer.state.clone(),
+                       "global_step": torch.tensor([trainer.global_step]), "sched_epoch": torch.tensor([trainer.sched_epoch])}
     batch = synthetic_batch(args.batch, args.res, dev, 42 + rank)         # data-parallel: different samples per rank
     noisy = DDPMScheduler().add_noise(batch["latents"], batch["noise"], batch["timesteps"]).half()
 
     def eager_step():
-        trainer.step(noisy, batch["timesteps"], batch["ehs"], batch["guide"], batch["noise"])
+        return trainer.step(noisy, batch["timesteps"], batch["ehs"], batch["guide"], batch["noise"])
 
     graphed = not args.no_graph
     if graphed:
@@ -528,17 +589,21 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # Timed region: `--windows` (default 3) back-to-back windows of EXACTLY --steps steps, each bracketed by barrier +
+    # Timed region: `--windows` (default 1, with --full 3) back-to-back windows of EXACTLY --steps steps, each bracketed by barrier +
     # synchronize on both sides and reduced with MAX over ranks as the contract says; the line reports the MEDIAN window as
     # value / ms_per_step and every window beside it, so a reader can see the spread (clock ramps, a noisy neighbour).
     windows = []
-    for _ in range(max(1, args.windows)):
+    pred = None
+    n_windows = max(1, args.windows)
+    for w in range(n_windows):
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if start_state is not None and w == n_windows - 1 and i == args.steps - 1:
+                trainer.load_state_dict(start_state)
+            pred = step()
         torch.cuda.synchronize()
         if world > 1:
             torch.distributed.barrier()
@@ -555,8 +620,19 @@ def main():
     loss = trainer.loss(noisy.numel())
     skipped = float(trainer.state[6])
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (which started from `start_state`): the UNet's noise prediction,
+        # the loss, the adapter parameters after the optimizer update and the (unscaled) gradients that update used, both in
+        # control_lora.parameters() order
+        params = torch.cat([p.detach().reshape(-1) for p in clora.parameters() if p.requires_grad])
+        dumped = dump_outputs(args.dump_outputs, {
+            "pred": pred, "loss": torch.tensor([loss], dtype=torch.float64),
+            "params": params, "grads": trainer.unscaled_grads_module_order()})
+        del params
+
     allreduce_ms = None
-    if world > 1 or trainer.comm == "clora":      # the exchange step on its own: 10 flat-buffer all-reduces, HIP events (with --comm clora also
+    if args.full and (world > 1 or trainer.comm == "clora"):      # the exchange step on its own: 10 flat-buffer all-reduces, HIP events (with --comm clora also
         #                                            at one rank: the C ABI's communicator / all-reduce call path on hardware, no peer traffic)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         keep = trainer.flat.grad.clone()           # through the trainer's own exchange path (torch process group or the C ABI)
@@ -744,7 +820,8 @@ def main():
 
     LEG_SECONDS['cpu_baseline'] = time.perf_counter() - _t_leg
     if rank == 0:
-        print("bench legs (s):", {k: round(v, 1) for k, v in LEG_SECONDS.items()}, file=sys.stderr)
+        if args.full:
+            print("bench legs (s):", {k: round(v, 1) for k, v in LEG_SECONDS.items()}, file=sys.stderr)
         print(json.dumps({
             "metric": "train images/sec SD-1.5+ControlLoRA 512^2 bs4/GPU", "value": round(images_per_s, 3),
             "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -768,7 +845,8 @@ def main():
             "gn_team_errors": K.gn_team_errors(dev),
             # compensated residual trunk (kernels.TrunkLo): "infer" = the samplers / validation only (the train step above is unaffected)
             "trunk_lo": K.TRUNK_LO_MODE,
-            "roofline": roofline, "ddim50": ddim, "full_step_with_vae_clip": full, "cpu_baseline": cpu}))
+            "roofline": roofline, "ddim50": ddim, "full_step_with_vae_clip": full, "cpu_baseline": cpu,
+            "full": args.full, "dumped_outputs": dumped}))
     trainer.close()
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -1,6 +1,8 @@
 """CPU tests: the oracle restatement against (a) the committed golden vectors made by the
-reference's own models.py, (b) the reference executed in place (build container only), and
-(c) the substitute pins of SURVEY.md section 8c (param counts, key sets, zero-init identity)."""
+reference's own models.py, (b) what the reference computes on small cases, recorded by running it in place
+(oracle/make_reference_records.py -> tests/golden/reference_records.*), and (c) the substitute pins of
+SURVEY.md section 8c (param counts, key sets, zero-init identity)."""
+import json
 import os
 
 import pytest
@@ -10,7 +12,7 @@ from safetensors.torch import load_file
 from oracle import cases, unet_ref
 from oracle import controllora_ref as cr
 
-HAVE_REF = os.path.isdir("/root/reference")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALL_CASES = list(cases.CASES) + ["lora"]
 
 
@@ -27,52 +29,54 @@ def test_oracle_matches_golden(case, golden_dir):
         assert err < 2e-5, f"{case}:{k} rel-L2 {err:.3e}"
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="/root/reference only exists in the build container")
+def chain_modules(impl, case, cad):
+    """(control processor, pre LoRA, post LoRA) of `impl` (the reference's models module or oracle.controllora_ref)"""
+    if impl is cr:
+        proc = (cr.ControlLoRAProcRef(64, cad, rank=4) if case == "v1" else
+                cr.ControlLoRAProcV2Ref(64, cad, rank=4, control_channels=32))
+        return proc, cr.LoRAProcRef(64, cad, rank=4), cr.LoRAProcRef(64, cad, rank=2, post_add=True)
+    proc = (impl.ControlLoRACrossAttnProcessor(64, cad, rank=4) if case == "v1" else
+            impl.ControlLoRACrossAttnProcessorV2(64, cad, rank=4, control_channels=32))
+    return proc, impl.LoRACrossAttnProcessor(64, cad, rank=4), impl.LoRACrossAttnProcessor(64, cad, rank=2, post_add=True)
+
+
 @pytest.mark.parametrize("case", ["v1", "v2"])
-def test_oracle_matches_reference_with_adapter_chain(case):
+def test_oracle_matches_reference_with_adapter_chain(case, golden_dir):
     """pre_loras / post_loras chaining (reference models.py:232-243, 249-265, 276-282;
-    mix_lora_and_control_lora.py:111-123) -- reference in place vs restatement."""
-    from oracle.diffusers_shim import import_reference_models
-    ref = import_reference_models()
-    torch.manual_seed(0)
-    attn = unet_ref.CrossAttention(64, None, heads=4, dim_head=16)
+    mix_lora_and_control_lora.py:111-123) -- restatement vs the reference's output recorded in place
+    with the same weights and inputs (oracle/make_reference_records.py)."""
+    rec = load_file(os.path.join(golden_dir, "reference_records.safetensors"))
     for self_attn in (True, False):
-        attn = unet_ref.CrossAttention(64, None if self_attn else 48, heads=4, dim_head=16)
+        head = f"chain.{case}.{'self' if self_attn else 'cross'}."
+        part = lambda name: {k[len(head + name) + 1:]: v for k, v in rec.items() if k.startswith(head + name + ".")}
         cad = None if self_attn else 48
-        if case == "v1":
-            a = ref.ControlLoRACrossAttnProcessor(64, cad, rank=4)
-            b = cr.ControlLoRAProcRef(64, cad, rank=4)
-        else:
-            a = ref.ControlLoRACrossAttnProcessorV2(64, cad, rank=4, control_channels=32)
-            b = cr.ControlLoRAProcV2Ref(64, cad, rank=4, control_channels=32)
-        pre_a, pre_b = ref.LoRACrossAttnProcessor(64, cad, rank=4), cr.LoRAProcRef(64, cad, rank=4)
-        post_a, post_b = ref.LoRACrossAttnProcessor(64, cad, rank=2, post_add=True), cr.LoRAProcRef(64, cad, rank=2, post_add=True)
-        for m, s in ((a, 1), (pre_a, 2), (post_a, 3)):
-            cases.seeded_weights_(m, seed=s)
-        b.load_state_dict(a.state_dict()); pre_b.load_state_dict(pre_a.state_dict()); post_b.load_state_dict(post_a.state_dict())
-        a.inject_pre_lora(pre_a); a.inject_post_lora(post_a)
+        attn = unet_ref.CrossAttention(64, cad, heads=4, dim_head=16)
+        attn.load_state_dict(part("attn"))
+        b, pre_b, post_b = chain_modules(cr, case, cad)
+        b.load_state_dict(part("proc")); pre_b.load_state_dict(part("pre")); post_b.load_state_dict(part("post"))
         b.inject_pre_lora(pre_b); b.inject_post_lora(post_b)
-        h = torch.randn(2, 16, 64)
-        e = None if self_attn else torch.randn(2, 5, 48)
-        ctrl = torch.randn(1, 64 if case == "v1" else 32, 4, 4)       # control batch 1 broadcasts (C6)
-        a.inject_control_states(ctrl); b.inject_control_states(ctrl.clone())
-        ya = a(attn, h, e, None, 0.7)
-        yb = b(attn, h, e, None, 0.7)
-        assert torch.allclose(ya, yb, atol=1e-6), float((ya - yb).abs().max())
+        b.inject_control_states(rec[head + "ctrl"].clone())
+        yb = b(attn, rec[head + "h"], None if self_attn else rec[head + "e"], None, 0.7)
+        ya = rec[head + "y"]
+        assert ya.shape == yb.shape and torch.allclose(ya, yb, atol=1e-6), float((ya - yb).abs().max())
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="/root/reference only exists in the build container")
 @pytest.mark.parametrize("name,n_params,n_keys", [
     ("fill50k", 6047040, 400), ("diffusiondb-canny", 6047040, 400), ("mpii-pose", 6047040, 400),
     ("post-add", 6048576, 400), ("danbooru-sketch", 19810304, 376),
     ("mpii-pose-v2", 5000704, 312), ("diffusiondb-canny-v2", 5000704, 312)])
-def test_param_counts_and_keys_vs_reference_configs(name, n_params, n_keys):
-    from oracle.diffusers_shim import import_reference_models
-    ref = import_reference_models()
-    path = f"/root/reference/configs/{name}.json"
-    a, b = ref.ControlLoRA.from_config(path), cr.ControlLoRARef.from_config(path)
-    assert sum(p.numel() for p in b.parameters()) == n_params == sum(p.numel() for p in a.parameters())
-    assert set(a.state_dict()) == set(b.state_dict()) and len(b.state_dict()) == n_keys
+def test_param_counts_and_keys_vs_reference_configs(name, n_params, n_keys, golden_dir):
+    """the reference's ControlLoRA built from its own configs/<name>.json (recorded in place: parameter count, state-dict keys
+    and shapes) vs the restatement built from this repository's copy of that config"""
+    with open(os.path.join(golden_dir, "reference_records.json")) as f:
+        ref = json.load(f)[f"configs.{name}"]
+    path = os.path.join(ROOT, "configs", f"{name}.json")
+    with open(path) as f:
+        assert json.load(f) == ref["config"]
+    b = cr.ControlLoRARef.from_config(path)
+    assert sum(p.numel() for p in b.parameters()) == n_params == ref["n_params"]
+    shapes = {k: list(v.shape) for k, v in b.state_dict().items()}
+    assert shapes == ref["state_dict_shapes"] and len(shapes) == n_keys
 
 
 def test_sd15_unet_parameter_count():
