@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Command-line form of the reference app's `process()` (reference apps/gradio_canny2image.py:66-92) on the MI355X path:
-resize the input image, Canny edge map (numpy implementation below: gradio / OpenCV are not in this image), control
+resize the input image, Canny edge map (numpy implementation, or the HIP detector with `--detector device`: gradio / OpenCV are not in this image), control
 tensor = edges / 127.5 - 1, hint-encode once per sample, CFG sampling (DPM-Solver++ like the app, or DDIM), VAE decode.
 
     python apps/canny2image.py --base /path/to/stable-diffusion-v1-5 --control_lora /path/to/control-lora \\
@@ -45,12 +45,24 @@ def resize_image(img: np.ndarray, resolution: int) -> np.ndarray:
 from controllora_amd.process import canny          # noqa: E402  (numpy Canny: shared with the process/diffusiondb_canny data set)
 
 
+def detect(img: np.ndarray, low, high, detector: str = "numpy", device="cuda") -> np.ndarray:
+    """uint8 [H,W,3] -> uint8 {0, 255} edge map [H,W] with the numpy detector or the device one"""
+    if detector == "numpy":
+        return canny(img, low, high)
+    if detector != "device":
+        raise ValueError(f"detector must be 'numpy' or 'device', got {detector!r}")
+    import torch
+    from controllora_amd import kernels as K
+    return K.canny(torch.from_numpy(np.ascontiguousarray(img)).to(device), min(low, high), max(low, high)).cpu().numpy()
+
+
 def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, sample_steps, scale, seed, eta,
-            low_threshold, high_threshold, sampler="dpm"):
-    """reference argument order; `eta` is accepted for compatibility (both samplers here are deterministic, eta = 0)"""
+            low_threshold, high_threshold, sampler="dpm", detector="numpy"):
+    """reference argument order; `eta` is accepted for compatibility (both samplers here are deterministic, eta = 0);
+    `detector="device"` makes the edge map with the HIP detector (controllora_amd.kernels.canny) instead of the numpy one"""
     import torch
     img = resize_image(hwc3(input_image), image_resolution)
-    detected_map = hwc3(canny(img, low_threshold, high_threshold))
+    detected_map = hwc3(detect(img, low_threshold, high_threshold, detector))
     control = torch.from_numpy(detected_map[..., ::-1].copy().transpose(2, 0, 1)).float()[None] / 127.5 - 1.0
     if seed == -1:
         seed = random.randint(0, 65535)
@@ -76,13 +88,14 @@ def main(argv=None):
     ap.add_argument("--low_threshold", type=int, default=100)
     ap.add_argument("--high_threshold", type=int, default=200)
     ap.add_argument("--sampler", default="dpm", choices=["dpm", "ddim"])
+    ap.add_argument("--detector", default="numpy", choices=["numpy", "device"], help="Canny on the CPU (numpy) or on the GPU (HIP kernels)")
     ap.add_argument("--out", default="canny2image.png")
     a = ap.parse_args(argv)
     from PIL import Image
     from controllora_amd.pipeline import ControlLoRAPipeline
     pipe = ControlLoRAPipeline.from_pretrained(a.base, a.control_lora)
     results = process(pipe, np.asarray(Image.open(a.input).convert("RGB")), a.prompt, a.a_prompt, a.n_prompt, a.num_samples,
-                      a.image_resolution, a.sample_steps, a.scale, a.seed, a.eta, a.low_threshold, a.high_threshold, a.sampler)
+                      a.image_resolution, a.sample_steps, a.scale, a.seed, a.eta, a.low_threshold, a.high_threshold, a.sampler, a.detector)
     Image.fromarray(np.concatenate(results, axis=1)).save(a.out)
     print("wrote", a.out)
 

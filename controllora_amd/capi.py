@@ -102,6 +102,7 @@ LORA_MAX_JOBS = 16
 LORA_WGRAD_MAX_JOBS = 32       # CLORA_LORA_WGRAD_MAX_JOBS
 WGRAD_JOBS_PER_LAUNCH = min(LORA_WGRAD_MAX_JOBS, max(1, int(os.environ.get("CLORA_WGRAD_JOBS", "32"))))   # A/B runs: 16 = the round-5 batching
 CONV_MAX_JOBS = 32
+CANNY_MAX_GROUP = 64           # CLORA_CANNY_MAX_GROUP
 _P, _I, _Z, _F = C.c_void_p, C.c_int, C.c_size_t, C.c_float
 _PROTOS = {
     "clora_gemm_f16": [_P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _P, _Z, _P],
@@ -162,6 +163,9 @@ _PROTOS = {
     "clora_grad_sumsq_f32": [_P, _Z, _P, _P],
     "clora_optim_prep_f32": [_P, _F, _F, _F, _I, _F, _F, _I, _P],
     "clora_adamw_flat_f32": [_P, _P, _P, _P, _Z, _P, _F, _F, _F, _F, _F, _P],
+    "clora_canny_classify_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "clora_canny_hysteresis_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "clora_canny_emit": [_P, _P, _P, _I, _I, _I, _P],
     "clora_abi_version": [],
     "clora_clock_probe": [_P, _I, _I, _P],
     "clora_groupnorm_workspace_bytes": [_I, _I, _I, _I, _I, _I],

@@ -81,8 +81,12 @@ class ImageGuideDataset(torch.utils.data.Dataset):
 
 
 def collate(examples: List[dict]) -> Dict[str, torch.Tensor]:
-    out = {"pixel_values": torch.stack([e["pixel_values"] for e in examples]).float(),
-           "guide_values": torch.stack([e["guide_values"] for e in examples]).float()}
+    out = {"pixel_values": torch.stack([e["pixel_values"] for e in examples]).float()}
+    if "guide_values" in examples[0]:
+        out["guide_values"] = torch.stack([e["guide_values"] for e in examples]).float()
+    else:                                   # process.DiffusionDBCanny(detector="device"): guides are made on the GPU (process.device_guides)
+        for k in ("canny_image", "canny_low", "canny_high"):
+            out[k] = torch.stack([e[k] for e in examples])
     if "input_ids" in examples[0]:
         out["input_ids"] = torch.stack([e["input_ids"] for e in examples])
     return out

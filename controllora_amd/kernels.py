@@ -914,3 +914,74 @@ def optim_prep(state, max_norm, beta1, beta2, dynamic, growth=2.0, backoff=0.5, 
 def adamw_flat(p, g, m, v, state, lr, beta1, beta2, eps, wd):
     _call("clora_adamw_flat_f32", ptr(p, f32), ptr(g, f32), ptr(m, f32), ptr(v, f32), p.numel(), ptr(state, f32), float(lr),
           float(beta1), float(beta2), float(eps), float(wd))
+
+
+# ------------------------------------------------------------------ Canny edge detector (control map of the canny data set / app)
+u8 = torch.uint8
+_CANNY_GROUPS = (4, 8, 16, 32, capi.CANNY_MAX_GROUP)       # passes enqueued per host readback: short first (ordinary images settle in
+                                                            # a few passes), then doubling (a long weak chain needs one pass per tile it crosses)
+
+
+def canny_classify(img_u8: torch.Tensor, low: torch.Tensor, high: torch.Tensor) -> torch.Tensor:
+    """uint8 images [B,H,W,C] (C = 3 RGB or 1 grey) and per-image fp32 thresholds `low`, `high` [B] on the images' device
+    -> uint8 class map [B,H,W]: 0 none, 1 weak, 2 strong
+    (`controllora_amd.process.canny` up to its hysteresis loop; include/clora.h clora_canny_classify_u8)"""
+    assert img_u8.dim() == 4 and img_u8.dtype == u8 and img_u8.is_contiguous() and img_u8.shape[-1] in (1, 3), "uint8 [B,H,W,C], C = 1 or 3"
+    B, H, W, Cc = img_u8.shape
+    assert low.shape == (B,) and high.shape == (B,) and low.device == img_u8.device and high.device == img_u8.device
+    cls = torch.empty((B, H, W), dtype=u8, device=img_u8.device)
+    _call("clora_canny_classify_u8", ptr(img_u8, u8), ptr(low.contiguous(), f32), ptr(high.contiguous(), f32), ptr(cls), B, H, W, Cc,
+          nbytes=float(img_u8.numel() + cls.numel()))
+    return cls
+
+
+def canny_hysteresis(cls: torch.Tensor, guide: bool = False, stats: Optional[dict] = None) -> torch.Tensor:
+    """class map uint8 [B,H,W] -> uint8 {0, 255} edge map [B,H,W]: strong pixels plus every weak pixel 8-connected to one through weak
+    pixels (the hysteresis loop of `process.canny`, bit for bit); `guide=True` returns the trainer's guide tensor instead, fp16
+    [B,3,H,W] in {-1, +1}.  Passes are enqueued in groups and ONE word is read back per group (a host synchronisation each: the pass
+    count depends on the data, so this call cannot be captured into a hipGraph).  `stats`, if given, receives the number of
+    passes enqueued, groups and launches."""
+    assert cls.dim() == 3 and cls.dtype == u8 and cls.is_contiguous()
+    B, H, W = cls.shape
+    state = cls.clone()
+    flags = torch.empty(capi.CANNY_MAX_GROUP + 1, dtype=torch.int32, device=cls.device)
+    done, groups = 0, 0
+    while True:
+        n = _CANNY_GROUPS[min(groups, len(_CANNY_GROUPS) - 1)]
+        if done > H * W:
+            raise capi.CloraError(f"canny hysteresis did not reach its fixed point within H * W = {H * W} passes")
+        _call("clora_canny_hysteresis_u8", ptr(state), ptr(flags), done, n, B, H, W)
+        done, groups = done + n, groups + 1
+        if int(flags[n].item()) == 0:                      # the one readback of the group
+            break
+    out = torch.empty((B, 3, H, W), dtype=f16, device=cls.device) if guide else torch.empty((B, H, W), dtype=u8, device=cls.device)
+    _call("clora_canny_emit", ptr(state), None if guide else ptr(out), ptr(out) if guide else None, B, H, W)
+    if stats is not None:                                      # launches: the state copy, per group the flag words + its passes, emit
+        stats.update(passes=done, groups=groups, launches=1 + groups + done + 1)
+    return out
+
+
+def canny(img_u8: torch.Tensor, low, high, guide: bool = False, stats: Optional[dict] = None) -> torch.Tensor:
+    """Canny edge map of uint8 image(s) on the device: [B,H,W,C] (C = 3 RGB, 1 grey) -> uint8 {0, 255} [B,H,W], or with
+    `guide=True` the guide tensor fp16 [B,3,H,W] in {-1, +1}; a single image [H,W,3] / [H,W] gives [H,W] (guide: [1,3,H,W]).
+    `low` / `high`: a number for all images or B values (tensor or sequence)."""
+    single = img_u8.dim() == 2 or (img_u8.dim() == 3 and img_u8.shape[-1] in (1, 3))
+    x = img_u8
+    if x.dim() == 2:
+        x = x[None, :, :, None]
+    elif single:
+        x = x[None]
+    elif x.dim() == 3:
+        x = x[..., None]                                       # [B,H,W] grey batch
+    x = x.contiguous()
+    B = x.shape[0]
+
+    def thr(v):
+        t = v if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=f32)
+        t = t.to(device=x.device, dtype=f32).reshape(-1)
+        return t.expand(B).contiguous() if t.numel() == 1 else t
+    cls = canny_classify(x, thr(low), thr(high))
+    out = canny_hysteresis(cls, guide=guide, stats=stats)
+    if stats is not None:
+        stats["launches"] += 1                                 # the classify launch
+    return out[0] if (single and not guide) else out

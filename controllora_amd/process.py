@@ -2,7 +2,8 @@
 process/diffusiondb_canny.py:11-48, process/mpii_pose.py:10-46, process/danbooru_sketch.py:9-76; selected at
 train_text_to_image_control_lora.py:546-550).  SURVEY.md section 8 (f)4, CPU-side data path.
 
-One item = {"pixel_values" [3,h,w] in [-1,1], "guide_values" [3,h,w] in [-1,1], "input_ids"}; the random numbers are drawn from
+One item = {"pixel_values" [3,h,w] in [-1,1], "guide_values" [3,h,w] in [-1,1], "input_ids"} (the canny data set with
+`detector="device"` carries the uint8 crop and its thresholds instead of `guide_values`, see `device_guides`); the random numbers are drawn from
 torch's global generator in the reference's order (style -> crop x -> crop y -> Canny low -> Canny high), so a seeded run picks the
 crops / thresholds the reference would.  What differs, by necessity of this image:
 
@@ -137,20 +138,34 @@ class Dataset(torch.utils.data.Dataset):
             if guide_img is not None:
                 guide_img = guide_img.crop(box)
         img_u8 = np.asarray(img)
-        g = self._guide_array(img_u8, guide_img).astype(np.float32) / 127.5 - 1.0
-        g = torch.from_numpy(np.ascontiguousarray(g))
-        g = g[None].repeat(3, 1, 1) if g.dim() == 2 else g.permute(2, 0, 1)
-        out = {"pixel_values": torch.from_numpy(img_u8.astype(np.float32)).permute(2, 0, 1) / 127.5 - 1.0, "guide_values": g.float().contiguous()}
+        out = {"pixel_values": torch.from_numpy(img_u8.astype(np.float32)).permute(2, 0, 1) / 127.5 - 1.0}
+        out.update(self._guide_fields(img_u8, guide_img))
         if self.tokenizer is not None:
             out["input_ids"] = self.tokenizer([text])[0]
         return out
 
+    def _guide_fields(self, img_u8: np.ndarray, guide_img) -> dict:
+        g = self._guide_array(img_u8, guide_img).astype(np.float32) / 127.5 - 1.0
+        g = torch.from_numpy(np.ascontiguousarray(g))
+        g = g[None].repeat(3, 1, 1) if g.dim() == 2 else g.permute(2, 0, 1)
+        return {"guide_values": g.float().contiguous()}
+
 
 class DiffusionDBCanny(Dataset):
-    """reference process/diffusiondb_canny.py:11-48: random crop, Canny with two thresholds drawn in [1, 255) per item"""
+    """reference process/diffusiondb_canny.py:11-48: random crop, Canny with two thresholds drawn in [1, 255) per item.
 
-    def __init__(self, tokenizer, resolution=512, use_crop=True, rows=None, **kwargs):
+    `detector="numpy"` (default): the item carries `guide_values` made by `canny()` above, on the CPU.
+    `detector="device"`: the item carries the cropped image (`canny_image`, uint8 [h,w,3]) and its two thresholds (`canny_low`,
+    `canny_high`) instead, plain CPU data, so a data-loader worker never opens the GPU; `device_guides(batch, device)` turns the
+    collated batch into `guide_values` with one `kernels.canny` call in the training process.  The thresholds are drawn by the same
+    two `_draw(1, 255)` calls at the same place, so a seeded run consumes torch's global generator exactly as with "numpy"."""
+    DETECTORS = ("numpy", "device")
+
+    def __init__(self, tokenizer, resolution=512, use_crop=True, rows=None, detector="numpy", **kwargs):
         super().__init__(tokenizer, resolution, use_crop)
+        if detector not in self.DETECTORS:
+            raise ValueError(f"detector must be one of {self.DETECTORS}, got {detector!r}")
+        self.detector = detector
         if rows is None:
             from datasets import load_dataset
             rows = load_dataset("poloclub/diffusiondb", "2m_random_1k")["train"]
@@ -163,9 +178,31 @@ class DiffusionDBCanny(Dataset):
         item = self.rows[int(index)]
         return item["image"].convert("RGB"), None, item["prompt"]
 
-    def _guide_array(self, img_u8, guide_img):
+    def _thresholds(self):
         low, high = _draw(1, 255), _draw(1, 255)                         # low first
-        return canny(img_u8, min(low, high), max(low, high))
+        return min(low, high), max(low, high)
+
+    def _guide_array(self, img_u8, guide_img):
+        return canny(img_u8, *self._thresholds())
+
+    def _guide_fields(self, img_u8, guide_img):
+        if self.detector == "numpy":
+            return super()._guide_fields(img_u8, guide_img)
+        low, high = self._thresholds()
+        return {"canny_image": torch.from_numpy(np.array(img_u8)), "canny_low": torch.tensor(float(low)),
+                "canny_high": torch.tensor(float(high))}
+
+
+def device_guides(batch: dict, device) -> dict:
+    """A collated batch of `DiffusionDBCanny(detector="device")` items -> the same batch with `guide_values` (fp16 [B,3,h,w] in
+    {-1, +1} on `device`) in place of `canny_image` / `canny_low` / `canny_high`: ONE `kernels.canny` call for the batch.  A batch
+    without those fields is returned as it is."""
+    if "canny_image" not in batch:
+        return batch
+    from . import kernels as K
+    out = {k: v for k, v in batch.items() if k not in ("canny_image", "canny_low", "canny_high")}
+    out["guide_values"] = K.canny(batch["canny_image"].to(device), batch["canny_low"].to(device), batch["canny_high"].to(device), guide=True)
+    return out
 
 
 class _FolderPairs(Dataset):

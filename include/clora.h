@@ -523,6 +523,29 @@ int clora_optim_prep_f32(float* state, float max_norm, float beta1, float beta2,
 int clora_adamw_flat_f32(float* p, const float* g, float* m, float* v, size_t n, const float* state, float lr,
                          float beta1, float beta2, float eps, float weight_decay, void* stream);
 
+/* ---- Canny edge detector on the device (the control map of `process/diffusiondb_canny`, reference process/diffusiondb_canny.py:35-41
+ * `cv2.Canny(image, low, high)`, and of the canny app, reference apps/gradio_canny2image.py:72-75).  The numpy detector
+ * `controllora_amd.process.canny` is the specification; the contract has two stages (INTEGRATION.md "Canny"):
+ *
+ * classify: img uint8 [B,H,W,C], C = 3 (RGB) or 1 (grey); low / high: DEVICE fp32 [B], one pair per image (swapped where low > high,
+ *   as cv2.Canny does); cls uint8 [B,H,W]: 0 = no edge candidate, 1 = weak (survives non-maximum suppression, mag >= low),
+ *   2 = strong (mag >= high).  One launch.  Grey, Sobel and the L1 magnitude are numpy's fp32 values bit for bit; the gradient sector
+ *   is binned exactly (fp64 comparison against tan 22.5 / 67.5 deg) where numpy bins an fp32 atan2, so the class map equals numpy's at
+ *   every pixel whose gradient angle is not within fp32 atan2 noise of a sector boundary. */
+int clora_canny_classify_u8(const uint8_t* img, const float* low, const float* high, uint8_t* cls, int B, int H, int W, int C,
+                            void* stream);
+/* hysteresis: `state` uint8 [B,H,W] starts as a copy of the class map and is updated in place (weak pixels 8-connected to a strong one
+ *   through weak pixels become 2); given the same class map the fixed point is numpy's loop bit for bit.  One call enqueues a GROUP of
+ *   `npasses` (1 .. CLORA_CANNY_MAX_GROUP) passes and needs `flags`: npasses + 1 device words, written by the call.  Pass i of the
+ *   group returns at once when pass i - 1 changed nothing, so the caller reads flags[npasses] back once per group: zero = the fixed
+ *   point is reached, non-zero = call again with pass_base advanced by npasses.  No synchronisation inside the library and no waiting
+ *   between workgroups of a launch.  pass_base > H * W (more passes than pixels: impossible for a monotone growth) -> CLORA_ERR_ARG. */
+#define CLORA_CANNY_MAX_GROUP 64
+int clora_canny_hysteresis_u8(uint8_t* state, unsigned* flags, int pass_base, int npasses, int B, int H, int W, void* stream);
+/* emit: state map -> edges uint8 [B,H,W] in {0, 255} (or NULL) and / or guide fp16 [B,3,H,W] (or NULL): -1 for 0, +1 for 255, the
+ *   three channels equal -- what the data set's `edges / 127.5 - 1` gives, in the layout the hint encoder takes. */
+int clora_canny_emit(const uint8_t* state, uint8_t* edges, clora_half* guide, int B, int H, int W, void* stream);
+
 /* Box calibration (bench.py "calibration"): `blocks` workgroups of 4 waves issue iters x 8 independent dense MFMAs each on
  * pseudo-random operands; out[3b .. 3b+2] = {shader cycles, 100 MHz wall ticks, checksum} of block b.  No reference
  * counterpart: it exists so that a bench line can be normalised by the clock the box actually held (DVFS). */

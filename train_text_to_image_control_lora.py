@@ -74,6 +74,9 @@ def parse_args(argv=None):
     p.add_argument("--control_lora_config", type=str, required=True)
     # additions (not in the reference): eager launches instead of the captured hipGraph step
     p.add_argument("--no_hipgraph", action="store_true", help="do not capture the step into hipGraphs")
+    p.add_argument("--canny_detector", type=str, default="numpy", choices=["numpy", "device"],
+                   help="process/diffusiondb_canny only: where the Canny control map is made -- 'numpy' in the data-loader workers "
+                        "(one CPU core per image), 'device' on the GPU, one call per batch in the training process")
     args = p.parse_args(argv)
     env_local_rank = int(os.environ.get("LOCAL_RANK", -1))
     if env_local_rank != -1 and env_local_rank != args.local_rank:
@@ -90,7 +93,8 @@ def build_dataset(args, tokenizer):
         return data.SyntheticFill50k(args.resolution, n, seed=args.seed if args.seed is not None else 42, tokenizer=tokenizer)
     if args.dataset_name is not None and args.dataset_name.startswith("process/"):       # reference train...:546-550
         from controllora_amd import process
-        return process.Dataset.from_name(args.dataset_name)(tokenizer, resolution=args.resolution, use_crop=True)
+        extra = {"detector": args.canny_detector} if args.dataset_name == "process/diffusiondb_canny" else {}
+        return process.Dataset.from_name(args.dataset_name)(tokenizer, resolution=args.resolution, use_crop=True, **extra)
     from datasets import load_dataset
     if args.dataset_name is not None:
         ds = load_dataset(args.dataset_name, args.dataset_config_name, cache_dir=args.cache_dir)
@@ -105,6 +109,16 @@ def build_dataset(args, tokenizer):
     if args.max_train_samples is not None:
         rows = rows.shuffle(seed=args.seed).select(range(args.max_train_samples))
     return data.ImageGuideDataset(rows, args.image_column, args.guide_column, args.caption_column, args.resolution, tokenizer)
+
+
+def batch_to_device(batch, dev):
+    """-> (pixel_values, guide_values) fp16 on `dev`.  A batch of the canny data set with `--canny_detector device` carries uint8 crops
+    and thresholds; its guides are made here by one device Canny call (`process.device_guides`), before and outside the captured
+    step (the detector's pass count depends on the data).  Every other batch is only moved."""
+    if "canny_image" in batch:
+        from controllora_amd import process
+        batch = process.device_guides(batch, dev)
+    return batch["pixel_values"].to(dev, non_blocking=True).half(), batch["guide_values"].to(dev, non_blocking=True).half()
 
 
 def latest_checkpoint(output_dir):
@@ -225,8 +239,7 @@ def main(argv=None):
             if args.resume_from_checkpoint and epoch == first_epoch and step < resume_step:
                 continue
             with torch.no_grad():
-                pixel = batch["pixel_values"].to(dev, non_blocking=True).half()
-                guide = batch["guide_values"].to(dev, non_blocking=True).half()
+                pixel, guide = batch_to_device(batch, dev)
                 latents = vae.encode(pixel).latent_dist.sample() * vae.scaling_factor
                 noise = torch.randn_like(latents)
                 timesteps = torch.randint(0, noise_scheduler.num_train_timesteps, (latents.shape[0],), device=dev).long()
@@ -301,6 +314,9 @@ def run_validation(args, unet, control_lora, vae, text_encoder, tokenizer, datas
     uncond = text_encoder(tokenizer([""]).to(dev))[0].half()
     for i in range(args.num_validation_images):
         ex = dataset[i % len(dataset)]
+        if "canny_image" in ex:                                   # --canny_detector device: the item carries no guide yet
+            from controllora_amd import data, process
+            ex["guide_values"] = process.device_guides(data.collate([ex]), dev)["guide_values"][0].float().cpu()
         guide = ex["guide_values"][None].to(dev).half()
         lat = ddim_sample(unet, control_lora, guide, cond, uncond, steps=30, guidance_scale=7.5, generator=gen, sampler="dpm")
         img = vae.decode(lat.half() / vae.scaling_factor).sample.float().clamp(-1, 1)
