@@ -79,6 +79,20 @@ class LoraUpJob(C.Structure):
                 ("R", C.c_int), ("scale", C.c_float)]
 
 
+class LoraFoldMember(C.Structure):
+    """mirror of clora_lora_fold_member_t"""
+    _fields_ = [("up", C.c_void_p), ("down", C.c_void_p), ("ldu", C.c_int), ("ldd", C.c_int), ("r", C.c_int), ("scale", C.c_float)]
+
+
+LORA_FOLD_MAX_MEMBERS = 8      # CLORA_LORA_FOLD_MAX_MEMBERS
+
+
+class LoraFoldJob(C.Structure):
+    """mirror of clora_lora_fold_job_t"""
+    _fields_ = [("W", C.c_void_p), ("out", C.c_void_p), ("out_t", C.c_void_p), ("ldw", C.c_int), ("ldo", C.c_int), ("ldt", C.c_int),
+                ("rows", C.c_int), ("K", C.c_int), ("nmem", C.c_int), ("m", LoraFoldMember * LORA_FOLD_MAX_MEMBERS)]
+
+
 class LoraWgradJob(C.Structure):
     """mirror of clora_lora_wgrad_job_t"""
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("T", C.c_void_p), ("ldt", C.c_int), ("toff", C.c_int), ("G", C.c_void_p),
@@ -141,6 +155,7 @@ _PROTOS = {
     "clora_rank_compose_bwd_f32": [C.POINTER(RankSite), _I, _P, _P],
     "clora_lora_up_f16": [_P, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _F, _P],
     "clora_lora_up_multi_f16": [C.POINTER(LoraUpJob), _I, _P],
+    "clora_lora_fold_f16": [_P, _I, _P],
     "clora_lora_wgrad_f16": [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _Z, _P],
     "clora_comm_unique_id": [_P],
     "clora_comm_init": [_P, _I, _I],

@@ -425,6 +425,95 @@ extern "C" int clora_lora_up_multi_f16(const clora_lora_up_job_t* jobs, int njob
     return clora_check_launch();
 }
 
+// ------------------------------------------------------------------------------------------------
+// clora_lora_fold_f16: W' = fp16(W + sum_m s_m U_m D_m) in both operand layouts (include/clora.h).  Memory bound: one read of W, two
+// writes.  A block walks 64 x 64 tiles of its job; a thread owns 8 consecutive k of two rows (16-byte loads of W and of the down rows,
+// 16-byte stores of the forward operand), the rounded tile goes through LDS k-major and leaves as 16-byte stores of the transposed
+// operand.  The rank loop reads up / down straight from L2: at rank 4 that is 1/8 of the bytes of W.
+namespace {
+constexpr int kFoldTile = 64, kFoldLd = kFoldTile + 8;        // +8 halves: rows stay 16-byte aligned, the k-major writes spread over banks
+
+__device__ __forceinline__ bool fold_job_ok(const clora_lora_fold_job_t& j) {
+    if (!j.W || !j.out || j.rows <= 0 || j.K <= 0 || ((j.rows | j.K | j.ldw | j.ldo) & 7) || j.nmem < 0 || j.nmem > CLORA_LORA_FOLD_MAX_MEMBERS)
+        return false;
+    if (j.out_t && (j.ldt & 7)) return false;
+    for (int m = 0; m < j.nmem; ++m) {
+        const clora_lora_fold_member_t& a = j.m[m];
+        if (!a.up || !a.down || a.r <= 0 || a.r > 256 || (a.ldd & 3) || ((uintptr_t)a.down & 15)) return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(256) void lora_fold_kernel(const clora_lora_fold_job_t* table) {
+    __shared__ __attribute__((aligned(16))) half_t tile[kFoldTile * kFoldLd];      // tile[k][n]
+    const clora_lora_fold_job_t& j = table[blockIdx.y];
+    if (!fold_job_ok(j)) return;                             // block-uniform
+    const half_t* W = (const half_t*)j.W;
+    half_t* out = (half_t*)j.out;
+    half_t* out_t = (half_t*)j.out_t;
+    const int rows = j.rows, K = j.K, nmem = j.nmem;
+    const int tr = threadIdx.x >> 3, tc = threadIdx.x & 7;
+    const int tiles_k = (K + kFoldTile - 1) / kFoldTile, tiles = ((rows + kFoldTile - 1) / kFoldTile) * tiles_k;
+    for (int ti = blockIdx.x; ti < tiles; ti += gridDim.x) {  // block-uniform trip count
+        const int n0 = (ti / tiles_k) * kFoldTile, k0 = (ti % tiles_k) * kFoldTile;
+        const int k = k0 + tc * 8;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int nl = tr + 32 * h, n = n0 + nl;
+            const bool ok = k < K && n < rows;               // K % 8 == 0: a chunk of 8 is all-valid or all-out
+            half8 o = zero8();
+            if (ok) {
+                const half8 w = ld8(W + (size_t)n * j.ldw + k);
+                float acc[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+                for (int m = 0; m < nmem; ++m) {
+                    const clora_lora_fold_member_t& a = j.m[m];
+                    const float* __restrict__ up = a.up + (size_t)n * a.ldu;
+                    const float* __restrict__ down = a.down + k;
+                    float part[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) part[e] = 0.f;
+                    for (int q = 0; q < a.r; ++q) {
+                        const float u = up[q];
+                        const floatx4 d0 = *reinterpret_cast<const floatx4*>(down + (size_t)q * a.ldd);
+                        const floatx4 d1 = *reinterpret_cast<const floatx4*>(down + (size_t)q * a.ldd + 4);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { part[e] += u * d0[e]; part[4 + e] += u * d1[e]; }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) acc[e] += a.scale * part[e];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (half_t)((float)w[e] + acc[e]);
+                st8(out + (size_t)n * j.ldo + k, o);
+            }
+            if (out_t) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) tile[(tc * 8 + e) * kFoldLd + nl] = o[e];
+            }
+        }
+        if (out_t) {                                         // job-uniform: every thread of the block takes the barriers
+            __syncthreads();
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int kl = tr + 32 * h, kk = k0 + kl, n = n0 + tc * 8;
+                if (kk < K && n < rows) st8(out_t + (size_t)kk * j.ldt + n, ld8(tile + kl * kFoldLd + tc * 8));   // rows % 8 == 0
+            }
+            __syncthreads();                                 // the next tile overwrites the staging buffer
+        }
+    }
+}
+}  // namespace
+
+extern "C" int clora_lora_fold_f16(const clora_lora_fold_job_t* jobs, int njobs, void* stream) {
+    if (!jobs || njobs <= 0 || njobs > 65535) return CLORA_ERR_ARG;
+    // a 1280 x 1280 segment is 400 tiles; a whole model (128 jobs) fills the chip at 32 blocks per job, a lone job gets its tiles' worth
+    const int bx = njobs >= 8 ? 32 : 256;
+    hipLaunchKernelGGL(lora_fold_kernel, dim3(bx, njobs), dim3(256), 0, (hipStream_t)stream, jobs);
+    return clora_check_launch();
+}
+
 namespace {
 int wgrad_rows_per_block(int M, int N) {
     int rpb = 64;   // 4 waves x one 16-row batch; grow until the grid is at most ~256 blocks

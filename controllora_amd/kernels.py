@@ -680,6 +680,43 @@ def lora_up_multi(jobs):
         _call("clora_lora_up_multi_f16", arr, len(chunk), nbytes=sum(2.0 * j.M * j.N for j in chunk))
 
 
+def lora_fold_job(W, out, out_t, members):
+    """one problem of lora_fold_multi: out [rows, K] = fp16(W + sum scale * up . down) and out_t [K, rows] (or None) its transpose;
+    members = [(up [rows, r] fp32, down [r, K] fp32, scale), ...].  W / out / out_t may be row or column slices of packed operands.
+    The job table lives on the device, so everything the kernel relies on is checked here."""
+    rows, Kd = W.shape
+    assert W.dtype == f16 and out.dtype == f16 and W.stride(1) == 1 and out.stride(1) == 1 and tuple(out.shape) == (rows, Kd)
+    assert rows % 8 == 0 and Kd % 8 == 0 and W.stride(0) % 8 == 0 and out.stride(0) % 8 == 0 and out.stride(0) >= Kd, (rows, Kd)
+    assert W.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and out.data_ptr() != W.data_ptr()
+    if out_t is not None:
+        assert out_t.dtype == f16 and tuple(out_t.shape) == (Kd, rows) and out_t.stride(1) == 1 and out_t.stride(0) % 8 == 0
+        assert out_t.stride(0) >= rows and out_t.data_ptr() % 16 == 0
+    if len(members) > capi.LORA_FOLD_MAX_MEMBERS:
+        raise capi.CloraError(f"a fold job takes at most {capi.LORA_FOLD_MAX_MEMBERS} members, got {len(members)}")
+    job = capi.LoraFoldJob(ptr(W, f16), ptr(out, f16), ptr(out_t, f16) if out_t is not None else None, W.stride(0), out.stride(0),
+                           out_t.stride(0) if out_t is not None else 0, rows, Kd, len(members))
+    keep = [W, out, out_t]
+    for i, (up, down, scale) in enumerate(members):
+        r = down.shape[0]
+        assert up.dtype == f32 and down.dtype == f32 and tuple(up.shape) == (rows, r) and tuple(down.shape) == (r, Kd), (up.shape, down.shape)
+        assert 1 <= r <= 256 and up.stride(1) == 1 and down.stride(1) == 1 and down.stride(0) % 4 == 0 and down.data_ptr() % 16 == 0
+        job.m[i] = capi.LoraFoldMember(ptr(up, f32), ptr(down, f32), up.stride(0), down.stride(0), r, float(scale))
+        keep += [up, down]
+    job._keep = keep                               # the operands outlive the launch that is built from this job
+    return job
+
+
+def lora_fold_multi(jobs, device=None):
+    """every job in ONE launch over a device-resident table -> the table (keep it referenced until the launch has run)"""
+    assert jobs
+    device = device if device is not None else jobs[0]._keep[0].device
+    arr = (capi.LoraFoldJob * len(jobs))(*jobs)
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    _call("clora_lora_fold_f16", ptr(table), len(jobs),
+          nbytes=sum(6.0 * j.rows * j.K + sum(4.0 * j.m[i].r * (j.rows + j.K) for i in range(j.nmem)) for j in jobs))
+    return table
+
+
 def lora_down_multi(jobs):
     """several adapter down-projections (possibly over different inputs) in one launch"""
     for i in range(0, len(jobs), capi.LORA_MAX_JOBS):

@@ -80,3 +80,47 @@ def load_vae(name: str, device, seed: int = 1) -> V.AutoencoderKL:
     vae = V.AutoencoderKL(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in cfg.items() if k in keep})
     _load_into(vae, _read_state_dict(folder), _VAE_RENAMES)
     return vae.to(device)
+
+
+# ---- plain LoRA files in the diffusers layout (`AttnProcsLayers(unet.attn_processors)` / `save_attn_procs`): what the reference's
+# train_dreambooth_lora.py saves and its mix_lora_and_control_lora.py:124-130 loads on top of the ControlLoRA processors
+LORA_FILE_NAMES = ("pytorch_lora_weights.safetensors", "pytorch_lora_weights.bin", "diffusion_pytorch_model.safetensors",
+                   "diffusion_pytorch_model.bin")
+_LORA_PARTS = tuple(f"to_{p}_lora.{d}.weight" for p in ("q", "k", "v", "out") for d in ("down", "up"))
+
+
+def _read_lora_file(path: str):
+    if os.path.isdir(path):
+        hit = next((os.path.join(path, n) for n in LORA_FILE_NAMES if os.path.exists(os.path.join(path, n))), None)
+        if hit is None:
+            raise FileNotFoundError(f"none of {', '.join(LORA_FILE_NAMES)} under {path}")
+        path = hit
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path)
+    return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def load_lora_attn_procs(unet, path_or_state_dict) -> dict:
+    """-> {attention processor name of `unet`: models.LoRACrossAttnProcessor} carrying the weights of a diffusers-format LoRA:
+    keys `<attention module path>.processor.to_{q,k,v,out}_lora.{down,up}.weight`; rank and sizes are read off the tensor
+    shapes.  Accepts a state dict, a `.bin` / `.safetensors` file or a folder holding one of LORA_FILE_NAMES.  The processors
+    are created on the UNet's device, in fp32, frozen or not as the caller decides (they come back trainable, like any module)."""
+    from . import models
+    sd = path_or_state_dict if isinstance(path_or_state_dict, dict) else _read_lora_file(str(path_or_state_dict))
+    names = list(unet.attn_processors.keys())
+    want = {f"{n}.{part}" for n in names for part in _LORA_PARTS}
+    missing, extra = sorted(want - set(sd)), sorted(set(sd) - want)
+    if missing or extra:
+        raise ValueError(f"LoRA file does not match the UNet's attention sites: missing {missing[:4]} unexpected {extra[:4]}")
+    dev = next(unet.parameters()).device
+    procs = {}
+    for n in names:
+        site = unet.get_submodule(n[:-len(".processor")])
+        q_down, k_down = sd[f"{n}.to_q_lora.down.weight"], sd[f"{n}.to_k_lora.down.weight"]
+        rank, hidden = q_down.shape
+        cad = k_down.shape[1] if getattr(site, "is_cross", n.endswith("attn2.processor")) else None
+        proc = models.LoRACrossAttnProcessor(hidden, cad, rank=rank)
+        _load_into(proc, {part: sd[f"{n}.{part}"] for part in _LORA_PARTS})
+        procs[n] = proc.to(dev)
+    return procs

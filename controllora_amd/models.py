@@ -165,7 +165,8 @@ class grouped_text_kv:
         buckets = {}
         for attn in sites:
             p = attn.processor
-            if isinstance(p, LoRACrossAttnProcessor) and not p._needs_generic_path():
+            # (a site that runs on folded weights keeps its own projection: the group is built from the unfolded ones)
+            if isinstance(p, LoRACrossAttnProcessor) and not p._needs_generic_path() and not p._chain_members():
                 buckets.setdefault((attn.inner_dim, attn.to_k.weight.shape[1]), []).append(attn)
         e2 = _flat2(self.ehs)
         table = {}
@@ -245,8 +246,49 @@ class LoRACrossAttnProcessor(nn.Module):
         """post_add adapters read the projection they are added to, and chained (pre/post) adapters read earlier
         adapter outputs: those cannot ride in one GEMM epilogue.  They run the same kernels, unfused, in exactly
         the reference's order (`_generic_call`)."""
-        chain = list(getattr(self, "pre_loras", [])) + list(getattr(self, "post_loras", []))
-        return bool(self.post_add or chain)
+        chain = self._chain_members()
+        if self.post_add or not chain:
+            return bool(self.post_add)
+        return self._fold_blocker(chain) is not None       # frozen plain members ride in the frozen weights instead (fold_sites)
+
+    def _chain_members(self):
+        return list(getattr(self, "pre_loras", [])) + list(getattr(self, "post_loras", []))
+
+    def _fold_blocker(self, members=None):
+        """None if the chained adapters of this site may be folded into its frozen weights right now, else the reason they may
+        not.  A plain, non-post_add member reads exactly what its base projection reads (hidden states for q, text or hidden
+        states for k / v, the attention output for out), so while it is frozen the site is the fused site with W + s U D."""
+        members = self._chain_members() if members is None else members
+        if not getattr(self, "fold_chain", False):
+            return "fold_chain is off"
+        if not members:
+            return "no chained adapters"
+        if self.post_add:
+            return "the main processor is post_add"
+        if len(members) > K.capi.LORA_FOLD_MAX_MEMBERS:
+            return f"more than {K.capi.LORA_FOLD_MAX_MEMBERS} chained adapters"
+        kv_in = self.cross_attention_dim or self.hidden_size
+        for m in members:
+            if type(m) is not LoRACrossAttnProcessor:
+                return f"a member is a {type(m).__name__}, not a plain LoRACrossAttnProcessor"
+            if m.post_add:
+                return "a member is post_add"
+            if m.hidden_size != self.hidden_size or (m.cross_attention_dim or m.hidden_size) != kv_in:
+                return "a member has other sizes than the site"
+            if any(q.dtype != f32 for q in m.parameters()):
+                return "a member is not held in fp32"
+        if torch.is_grad_enabled() and any(q.requires_grad for m in members for q in m.parameters()):
+            return "a member is trainable and autograd is on"
+        return None
+
+    def _site_packs(self, attn, scale):
+        """-> (q|k|v packs, out pack, fold generation) of the fused path: the module's own (generation None), or the folded ones
+        when adapters are chained on (only reached with a chain that folds: `_needs_generic_path`)"""
+        if not self._chain_members():
+            return attn.fused_packs(), attn.to_out[0].pack(), None
+        fold_sites([(self, attn)], scale)
+        st = self.__dict__["_fold"]
+        return st["packs"], st["out_pack"], st["gen"]
 
     def _generic_call(self, attn, hidden_states, encoder_hidden_states, scale, residual):
         """Reference order, one kernel group per adapter (models.py:118-152, 222-287, 357-431 incl. quirks C2/C3)."""
@@ -300,7 +342,7 @@ class LoRACrossAttnProcessor(nn.Module):
         return out.reshape(B, N, C_)
 
     def _attend(self, attn, h2, q_in, e2, B, N, Nk, scale, out_in_fn, residual, own_out_always, t_pre=None):
-        packs = attn.fused_packs()
+        packs, out_pack, fold_gen = self._site_packs(attn, scale)
         # t_pre: the control term's share of the q adapter's down-projection -- in rank space (ops.control_terms_rank: q_in is
         # the hidden states alone then), or, with the materialised term (q_in = (h, c)), c . D_q^T evaluated for the whole level
         # in one launch (ops.control_q_parts; only meaningful with that very c)
@@ -314,7 +356,9 @@ class LoRACrossAttnProcessor(nn.Module):
                 a = ops.attention_cross_grouped(q, grp[0], grp[1], B, attn.heads, N, Nk, attn.dim_head, attn.scale)
             else:
                 cache = _TEXT_KV if not torch.is_grad_enabled() else None
-                key = (id(self), id(attn), e2.data_ptr(), e2._version, tuple(e2.shape), float(scale)) if cache is not None else None
+                # (the fold generation: K / V of other folded weights -- a changed chain, member or scale -- are never served)
+                key = (id(self), id(attn), e2.data_ptr(), e2._version, tuple(e2.shape), float(scale),
+                       fold_gen) if cache is not None else None
                 kv = cache.get(key) if cache is not None else None
                 if kv is None:
                     kv = ops.lora_proj(e2, packs[1], [self._seg("to_k_lora", e2, scale, self.key_states_skipped),
@@ -330,7 +374,7 @@ class LoRACrossAttnProcessor(nn.Module):
         a = out_in_fn(a)
         out_seg = self._seg("to_out_lora", a, scale, (not own_out_always) and self.output_states_skipped)
         res2 = _flat2(residual) if residual is not None else None
-        return ops.lora_proj(a, attn.to_out[0].pack(), [out_seg], residual=res2)
+        return ops.lora_proj(a, out_pack, [out_seg], residual=res2)
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, scale=1.0, residual=None):
         attn = _host(attn, encoder_hidden_states)
@@ -345,7 +389,62 @@ class LoRACrossAttnProcessor(nn.Module):
         return out.reshape(B, N, C_)
 
 
+_FOLD_GEN = [0]
+
+
+def fold_sites(pairs, scale=1.0):
+    """Bring the folded operands of the given (processor, attention host) sites up to date -- every stale site in ONE launch
+    (kernels.lora_fold_multi) -- and leave them on the processor (`_fold`).  A fold is keyed on the base packs (storage /
+    version of the frozen weights), every member parameter's storage / version, the chain's members in order with their skip
+    flags, the main processor's version and `scale`: an in-place update, load_state_dict, another scale or an edited chain
+    refolds.  Scaling quirks as in `_generic_call`: a member's value adapter is scaled by `scale` only under a version-0 main
+    processor, else by 1.0 (C3); a member's key / value / out adapter is left out when that member's own skip flag is set.
+    -> number of sites that were (re)folded."""
+    scale = float(scale)
+    jobs, fresh = [], []
+    for proc, attn in pairs:
+        members = proc._chain_members()
+        why = proc._fold_blocker(members)
+        if why is not None:
+            raise RuntimeError(f"this site's chained adapters cannot be folded: {why}")
+        version = getattr(proc, "version", 0)
+        base, base_out = attn.fused_packs(), attn.to_out[0].pack()
+        key = (tuple((id(b), b.w.data_ptr(), b.w._version) for b in base + (base_out,)), scale, version,
+               tuple((id(m), m.key_states_skipped, m.value_states_skipped, m.output_states_skipped,
+                      tuple((q.data_ptr(), q._version) for q in m.parameters())) for m in members))
+        st = proc.__dict__.get("_fold")
+        if st is not None and st["key"] == key:
+            continue
+        if K.capi.lib().require_device and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a chained adapter, its scale or the frozen weights changed inside a graph capture: run one forward "
+                               "(or ControlLoRA.fold_now) before capturing, the fold is not part of the captured step")
+        if st is None or st["base"] != tuple(id(b) for b in base + (base_out,)):
+            st = dict(packs=tuple(ops.FoldedPack(b) for b in base), out_pack=ops.FoldedPack(base_out),
+                      base=tuple(id(b) for b in base + (base_out,)), keep=base + (base_out,))
+        C_ = proc.hidden_size
+        vs = scale if version == 0 else 1.0                                                    # quirk C3
+        q = [(m.to_q_lora.up.weight.detach(), m.to_q_lora.down.weight.detach(), scale) for m in members]
+        k = [(m.to_k_lora.up.weight.detach(), m.to_k_lora.down.weight.detach(), scale) for m in members if not m.key_states_skipped]
+        v = [(m.to_v_lora.up.weight.detach(), m.to_v_lora.down.weight.detach(), vs) for m in members if not m.value_states_skipped]
+        o = [(m.to_out_lora.up.weight.detach(), m.to_out_lora.down.weight.detach(), scale) for m in members if not m.output_states_skipped]
+        if len(base) == 2:                                                                     # cross-attention: q and k|v
+            jobs += st["packs"][0].jobs([(0, C_, q)]) + st["packs"][1].jobs([(0, C_, k), (C_, C_, v)])
+        else:
+            jobs += st["packs"][0].jobs([(0, C_, q), (C_, C_, k), (2 * C_, C_, v)])
+        jobs += st["out_pack"].jobs([(0, st["out_pack"].N, o)])
+        fresh.append((proc, st, key))
+    if jobs:
+        K.lora_fold_multi(jobs)
+    for proc, st, key in fresh:
+        _FOLD_GEN[0] += 1
+        st["key"], st["gen"] = key, _FOLD_GEN[0]
+        proc.__dict__["_fold"] = st
+    return len(fresh)
+
+
 class _ControlMixin:
+    fold_chain = False        # opt-in: frozen plain LoRAs chained onto this site ride in its frozen weights (fold_sites)
+
     def inject_pre_lora(self, lora_layer):
         self.pre_loras.append(lora_layer)
 
@@ -679,6 +778,34 @@ class ControlLoRA(nn.Module):
         model.load_state_dict(sd)
         return model
 
+    # ---- frozen LoRAs chained onto the sites (inject_pre_lora / inject_post_lora) folded into the frozen weights
+    def _named_processors(self):
+        return [(f"lora_layers.{i}.{j}", p) for i, level in enumerate(self.lora_layers) for j, p in enumerate(level)]
+
+    def fold_chains(self, enabled: bool = True):
+        """opt in (or out): every site whose chain is eligible (`fold_report`) runs the fused path on W + s U D"""
+        for _, p in self._named_processors():
+            p.fold_chain = bool(enabled)
+            if not enabled:
+                p.__dict__.pop("_fold", None)
+        return self
+
+    def fold_report(self) -> dict:
+        """per site: does its chain fold under the current autograd mode, and if not, why"""
+        rep = {}
+        for name, p in self._named_processors():
+            why = p._fold_blocker()
+            rep[name] = dict(folded=why is None, reason=why, members=len(p._chain_members()))
+        return rep
+
+    def fold_now(self, unet, scale: float = 1.0) -> int:
+        """fold every eligible site of `unet` that carries one of this model's processors in one launch, e.g. ahead of a graph
+        capture or after swapping LoRAs (a forward folds stale sites on its own, site by site) -> sites folded"""
+        mine = {id(p) for _, p in self._named_processors()}
+        pairs = [(m.processor, m) for m in unet.modules()
+                 if id(getattr(m, "processor", None)) in mine and hasattr(m, "fused_packs") and m.processor._fold_blocker() is None]
+        return fold_sites(pairs, scale)
+
     # ---- forward (H4, reference models.py:810-835)
     @staticmethod
     def _inject_control_terms(procs, c):
@@ -762,3 +889,25 @@ def map_processors_to_unet(unet, control_lora) -> dict:
         if pools[cid]:
             procs[name] = pools[cid].pop(0)
     return procs
+
+
+def mix_lora_into_control_lora(unet, control_lora, lora_procs, pre=True, post=False, fold=True) -> dict:
+    """Chain a plain LoRA (name -> LoRACrossAttnProcessor, e.g. from loading.load_lora_attn_procs) onto the ControlLoRA
+    processors site by site (reference mix_lora_and_control_lora.py:111-121; defaults as there: pre on, post off) and install
+    the ControlLoRA processors on the UNet (:132-151).  fold: freeze the LoRA and let every eligible site run on folded weights
+    (ControlLoRA.fold_chains; `fold_report()` tells which).  -> the installed name -> processor mapping."""
+    sites = map_processors_to_unet(unet, control_lora)
+    lacking = sorted(set(sites) - set(lora_procs))
+    if lacking:
+        raise ValueError(f"no LoRA processor for the sites {lacking[:4]}")
+    for name, proc in sites.items():
+        member = lora_procs[name]
+        if fold:
+            member.requires_grad_(False)
+        if pre:
+            proc.inject_pre_lora(member)
+        if post:
+            proc.inject_post_lora(member)
+    control_lora.fold_chains(bool(fold))
+    unet.set_attn_processor(sites)
+    return sites

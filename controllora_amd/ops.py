@@ -38,6 +38,23 @@ class LinearPack:
             self.bias = torch.cat([b, b.new_zeros(Np - N)]) if Np != N else b.contiguous()
 
 
+class FoldedPack:
+    """The LinearPack surface (w, wt, bias, N, K) over operands that `kernels.lora_fold_multi` writes: W' = W + sum s U D of the
+    frozen adapters chained onto a site (models.fold_sites).  The buffers are allocated once per base pack and refolded in place,
+    so a captured graph that replays launches over them keeps valid addresses; the bias is the base pack's own."""
+
+    def __init__(self, base: LinearPack):
+        self.base = base
+        self.N, self.K, self.N_logical, self.bias = base.N, base.K, base.N_logical, base.bias
+        self.w = torch.empty_like(base.w)
+        self.wt = torch.empty_like(base.wt)
+
+    def jobs(self, segments):
+        """segments: [(first row, rows, [(up, down, scale), ...])] covering every row of the pack -> fold jobs"""
+        assert sorted((r0, r0 + n) for r0, n, _ in segments)[0][0] == 0 and sum(n for _, n, _ in segments) == self.N
+        return [K.lora_fold_job(self.base.w[r0:r0 + n], self.w[r0:r0 + n], self.wt[:, r0:r0 + n], members) for r0, n, members in segments]
+
+
 class GegluPack:
     """`FeedForward.net[0].proj` (Linear(C, 8C), upstream GEGLU) packed for the fused activation epilogue: the forward
     operand's rows (and the bias) are regrouped as [64 a-columns | the 64 matching g-columns] per 128 (include/clora.h

@@ -455,6 +455,32 @@ typedef struct {
     clora_half* Y; int ldy; int M, N, R; float scale;
 } clora_lora_up_job_t;
 int clora_lora_up_multi_f16(const clora_lora_up_job_t* jobs, int njobs, void* stream);
+/* Folds frozen rank-r adapters into a frozen projection weight -- a plain LoRA chained onto a ControlLoRA site with inject_pre_lora /
+ * inject_post_lora (reference mix_lora_and_control_lora.py:111-121) reads the very tensor its base projection reads, so while it is
+ * frozen the site is the plain site run with W' = W + sum_m scale_m * up_m . down_m:
+ *   out[n, k] = out_t[k, n] = fp16(W[n, k] + sum_m scale_m * sum_j up_m[n, j] * down_m[j, k])
+ * the sum formed in fp32 and rounded ONCE, however many members are stacked.  One job is one row segment of one packed operand (q of
+ * a q|k|v pack, the k or v half of a k|v pack, an out projection): `out` [rows, K] is the forward operand, `out_t` [K, rows] (may
+ * be NULL) the matching column slice of the dgrad operand; ldw / ldo / ldt are row pitches in elements.  nmem = 0 is a copy.
+ * rows, K and the pitches are multiples of 8, 1 <= r <= 256, down matrices are 16-byte aligned with ldd % 4 == 0, `out` / `out_t`
+ * do not alias W.  `jobs` is a DEVICE array of njobs jobs (as for clora_lora_pack_f16): one launch folds every site of a model;
+ * a job that breaks the contract above is left out by the kernel (nothing is written for it).  Deterministic: no atomics, every
+ * element is produced by one thread in a fixed order. */
+#define CLORA_LORA_FOLD_MAX_MEMBERS 8
+typedef struct {
+    const float* up;    /* [rows, r], row pitch ldu */
+    const float* down;  /* [r, K], row pitch ldd */
+    int ldu, ldd, r;
+    float scale;
+} clora_lora_fold_member_t;
+typedef struct {
+    const clora_half* W;
+    clora_half* out;
+    clora_half* out_t;
+    int ldw, ldo, ldt, rows, K, nmem;
+    clora_lora_fold_member_t m[CLORA_LORA_FOLD_MAX_MEMBERS];
+} clora_lora_fold_job_t;
+int clora_lora_fold_f16(const clora_lora_fold_job_t* jobs, int njobs, void* stream);
 /* G[n*gs_n + j*gs_j] += scale * sum_m A[m, n] * T[m, toff+j]  (adapter weight gradients; two-stage
  * deterministic reduction through `workspace` of clora_lora_wgrad_workspace_bytes(M, N, R) bytes, no atomics). */
 size_t clora_lora_wgrad_workspace_bytes(int M, int N, int R);
