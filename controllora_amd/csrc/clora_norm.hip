@@ -75,6 +75,28 @@ __device__ __forceinline__ GnColW gn_dx_col(const GnArgs& a, int ch0) {
     return c;
 }
 
+// The forward statistics are ONE pass over x (the input is read once for the sums, a bandwidth decision), and E[x^2] - mean^2 in
+// fp32 loses |mean|^2 / var * 2^-24 of the variance: 9e-4 of rstd at |mean| = 100 std (tests/kernel_cases.py::case_groupnorm_offset).
+// So every sum of a group is taken over x - P, with the pivot P = the group's first channel in row 0 of the batch element: a value
+// within a few std of the mean, read by every block that sums a part of the group (one L2-resident scalar per group), exact to
+// subtract from fp16 data of the same magnitude.  The partial sums stay plain sums, so every reduction stage is unchanged;
+// the last one turns (E[x - P], E[(x - P)^2]) into mean = P + E[x - P] and var = E[(x - P)^2] - E[x - P]^2.
+// P is re-read from x by blocks that may run after others have stored y, so y must not alias x (include/clora.h).
+// Cost: the pivots of a thread's channels stay live over the sums -- no scratch, but gn_fwd_resident_kernel<256,8> goes from 78 to 132
+// VGPRs and gn_fwd_team_kernel<512,16> from 124 to 141 (4 -> 3 waves per SIMD each), gn_fwd_partial_kernel<2> from 5 to 4.
+__device__ __forceinline__ float gn_pivot(const GnArgs& a, int b, int ch) {
+    if (a.x2 && ch >= a.Ca) return (float)a.x2[(size_t)b * a.HW * (a.C - a.Ca) + (ch - a.Ca)];
+    return (float)a.x[(size_t)b * a.HW * (a.x2 ? a.Ca : a.C) + ch];
+}
+// the pivots of the eight channels ch0 .. ch0 + 7 (one load per distinct group)
+__device__ __forceinline__ void gn_pivots8(const GnArgs& a, int b, int ch0, int cpg, float (&piv)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int g = (ch0 + e) / cpg;
+        piv[e] = (e > 0 && g == (ch0 + e - 1) / cpg) ? piv[e - 1] : gn_pivot(a, b, g * cpg);
+    }
+}
+
 // thread -> (row lane, first column chunk, column stride)
 __device__ __forceinline__ void gn_thread_map(int t, int CH, int& rl, int& nrl, int& c0, int& cstep, bool& active) {
     if (CH >= 256) { rl = 0; nrl = 1; c0 = t; cstep = 256; active = true; }
@@ -151,6 +173,9 @@ __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
         GnCol col[NJ];
 #pragma unroll
         for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; col[j] = gn_in_col(p, cb + (cc < CH ? cc : c0) * 8); }
+        float piv[NJ][8];                                        // see gn_pivot
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; gn_pivots8(p, b, cb + (cc < CH ? cc : c0) * 8, p.C / p.G, piv[j]); }
         const size_t brow = (size_t)b * p.HW;
         for (int it0 = 0; it0 < nit; it0 += kGnU) {
             half8 v[kGnU][NJ];
@@ -169,7 +194,7 @@ __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
                     CLORA_KEEP(v[u][j]);
                     if (c0 + j * cstep < CH) {                   // thread-constant
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[u][j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
+                        for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[u][j][e] - piv[j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
                     }
                 }
             }
@@ -281,11 +306,12 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
     const int CH = p.CS / 8, cpg = p.C / p.G;
     gn_fold_groups(p, b, t, mr, 1.0f / ((float)p.HW * (float)cpg));
     __syncthreads();
-    if (t < p.G) {                                  // (E[x], E[x^2]) -> (mean, rstd)
-        const float mean = mr[t * 2];
-        float var = mr[t * 2 + 1] - mean * mean;
+    if (t < p.G) {                                  // (E[x - P], E[(x - P)^2]) -> (mean, rstd), see gn_pivot
+        const float dm = mr[t * 2], mean = gn_pivot(p, b, t * cpg) + dm;
+        float var = mr[t * 2 + 1] - dm * dm;
         var = var < 0.f ? 0.f : var;
         const float rstd = rsqrtf(var + p.eps);
+        mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         if (chunk == 0 && blockIdx.y == 0) { p.stats[((size_t)b * p.G + t) * 2] = mean; p.stats[((size_t)b * p.G + t) * 2 + 1] = rstd; }
     }
@@ -516,6 +542,7 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
     __shared__ float red[NT * 16];                               // [nrl][CS][2] with nrl * CS <= NT * 8
     __shared__ float chs[256 * 8 * 2];                           // per-channel totals of the slab (CS <= 2048)
     __shared__ float mr[64 * 2];
+    __shared__ float pv[64];                                     // the pivot of each group of the slab
     const int t = threadIdx.x, b = blockIdx.z, cb = blockIdx.y * p.CS;
     const int CH = p.CS / 8, cpg = p.C / p.G, gps = p.G / p.nslab;
     const int nrl = NT / CH, rl = t / CH, c0 = t - rl * CH;
@@ -543,19 +570,33 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
                 v[k] = (k < npt) ? ld8(col.p + (brow + (size_t)(r < p.HW ? r : 0)) * col.pitch) : zero8();
             }
         }
+    }
+    // the pivots (gn_pivot) come from the registers of the threads that hold row 0 -- with DEF the stored x is not finished yet -- through
+    // chs, which gn_res_reduce only writes after its first barrier
+    if (active && rl == 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) chs[c0 * 8 + e] = (float)v[0][e];
+    }
+    __syncthreads();
+    if (t < gps) pv[t] = chs[t * cpg];
+    if (active) {
+        float piv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) piv[e] = chs[((c0 * 8 + e) / cpg) * cpg];
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = k < npt && rl + k * nrl < p.HW;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] : 0.f; s[e] += f; q[e] += f * f; }
+            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f / ((float)p.HW * (float)cpg));
-    if (t < gps) {                                               // (E[x], E[x^2]) -> (mean, rstd)
-        const float mean = mr[t * 2];
-        float var = mr[t * 2 + 1] - mean * mean;
+    if (t < gps) {                                               // (E[x - P], E[(x - P)^2]) -> (mean, rstd)
+        const float dm = mr[t * 2], mean = pv[t] + dm;
+        float var = mr[t * 2 + 1] - dm * dm;
         var = var < 0.f ? 0.f : var;
         const float rstd = rsqrtf(var + p.eps);
+        mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         float* st = p.stats + ((size_t)b * p.G + blockIdx.y * gps + t) * 2;
         st[0] = mean; st[1] = rstd;
@@ -758,20 +799,23 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
             const int r = r0 + rl + k * nrl;
             v[k] = ld8(col.p + (brow + (size_t)(r < r_end ? r : (r0 < p.HW ? r0 : 0))) * col.pitch);
         }
+        float piv[8];                                            // see gn_pivot: the same value in every member of the unit
+        gn_pivots8(p, b, cb + c0 * 8, cpg, piv);
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = r0 + rl + k * nrl < r_end;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] : 0.f; s[e] += f; q[e] += f * f; }
+            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f);
     if (!gn_team_exchange<NT>(p, u, m, s_epoch, gps * 2, mr, gat, 1.0f / ((float)p.HW * (float)cpg))) return;
-    if (t < gps) {                                               // (E[x], E[x^2]) -> (mean, rstd)
-        const float mean = mr[t * 2];
-        float var = mr[t * 2 + 1] - mean * mean;
+    if (t < gps) {                                               // (E[x - P], E[(x - P)^2]) -> (mean, rstd)
+        const float dm = mr[t * 2], mean = gn_pivot(p, b, cb + t * cpg) + dm;
+        float var = mr[t * 2 + 1] - dm * dm;
         var = var < 0.f ? 0.f : var;
         const float rstd = rsqrtf(var + p.eps);
+        mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         if (m == 0) {
             float* st = p.stats + ((size_t)b * p.G + (cb / cpg) + t) * 2;

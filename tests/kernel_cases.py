@@ -937,3 +937,410 @@ def case_gemm_trunk_lo(dev, M, N, K_, split_k=1, tile_cfg=0, conv_like=False, lo
     assert rel(plain[3], ref) > 1.2 * rel(hi[3], ref) or rel(plain[3], ref) < 3e-4
     again = K.gemm(As[1], W, M, N, K_, bias=bias, residual=plain[0], **kw)
     assert torch.equal(again, plain[1])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Every attention instantiation, both backward widths, the causal entry point and the option table against fp64 references.
+# Each case prints the figures it asserts on (pytest -s / -rP shows them): the record of what a run measured.
+
+# library defaults of the knobs the cases below move (g_opts in clora_gemm.hip); a value forwarded from the environment (capi._ENV_OPTIONS)
+# is what a case restores
+_OPTION_DEFAULTS = {"attn_fwd_waves": ("CLORA_ATTN_FWD_WAVES", 0), "attn_bwd_waves": ("CLORA_ATTN_BWD_WAVES", 0), "gn_blocks": ("CLORA_GN_BLOCKS", 512),
+                    "epi_two_phase": ("CLORA_EPI_TWO_PHASE", 1), "gn_unroll": ("CLORA_GN_UNROLL", 0), "epi_hoist": ("CLORA_EPI_HOIST", 1),
+                    "gn_resident": ("CLORA_GN_RESIDENT", 1), "wgrad_patch": ("CLORA_WGRAD_PATCH", 1), "strip_blocks": ("CLORA_STRIP_BLOCKS", 512),
+                    "gn_team": ("CLORA_GN_TEAM", 2)}
+
+
+def option_default(name):
+    var, val = _OPTION_DEFAULTS[name]
+    return int(os.environ.get(var) or val)
+
+
+class options:
+    """with options(attn_bwd_waves=8, ...): the knobs are set for the block and put back afterwards, whatever happens inside"""
+
+    def __init__(self, **kv):
+        self.kv = kv
+
+    def __enter__(self):
+        for k_, v_ in self.kv.items():
+            K.set_option(k_, v_)
+
+    def __exit__(self, *exc):
+        for k_ in self.kv:
+            K.set_option(k_, option_default(k_))
+        return False
+
+
+def rel64(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).norm() / (b.norm() + 1e-300))
+
+
+def _attn_ref64(q, k, v, dO, B, H, Nq, Nk, D, scale, causal=False):
+    """softmax(scale q k^T) v in fp64 on the fp16 inputs, one batch element at a time (the score tensor of a 4096-token site is 1 GiB per
+    element): o [B*Nq, H*D], lse [B, H, Nq], the three gradients for dO, and the per-row size of the logits' terms
+    scale * max_j sum_d |q_d k_jd| that the LSE bound of case_attention_full is built on."""
+    o, lse, mag, dq, dk, dv = [], [], [], [], [], []
+    heads = lambda t_, n: t_.double().reshape(n, H, D).permute(1, 0, 2)
+    rows = lambda t_, n: t_.permute(1, 0, 2).reshape(n, H * D)
+    for b in range(B):
+        qb = heads(q[b * Nq:(b + 1) * Nq], Nq).clone().requires_grad_(dO is not None)
+        kb = heads(k[b * Nk:(b + 1) * Nk], Nk).clone().requires_grad_(dO is not None)
+        vb = heads(v[b * Nk:(b + 1) * Nk], Nk).clone().requires_grad_(dO is not None)
+        s = qb @ kb.transpose(-1, -2) * scale
+        if causal:
+            s = s.masked_fill(torch.ones(Nq, Nk, dtype=torch.bool, device=s.device).triu(1), float("-inf"))
+        ob = torch.softmax(s, -1) @ vb
+        lse.append(torch.logsumexp(s.detach(), -1))
+        mag.append((qb.detach().abs() @ kb.detach().abs().transpose(-1, -2)).amax(-1) * scale)
+        o.append(rows(ob.detach(), Nq))
+        if dO is not None:
+            ob.backward(heads(dO[b * Nq:(b + 1) * Nq], Nq))
+            dq.append(rows(qb.grad, Nq)), dk.append(rows(kb.grad, Nk)), dv.append(rows(vb.grad, Nk))
+        del s, ob
+    out = dict(o=torch.cat(o), lse=torch.stack(lse), mag=torch.stack(mag))
+    if dO is not None:
+        out.update(dq=torch.cat(dq), dk=torch.cat(dk), dv=torch.cat(dv))
+    return out
+
+
+def attention_full_inputs(dev, B, H, Nq, Nk, D, q_scale=1.0, seed=51):
+    g = torch.Generator().manual_seed(seed)
+    scale = D ** -0.5
+    q = rnd((B * Nq, H * D), dev, g, q_scale)
+    k, v, dO = rnd((B * Nk, H * D), dev, g), rnd((B * Nk, H * D), dev, g), rnd((B * Nq, H * D), dev, g)
+    return dict(q=q, k=k, v=v, dO=dO, scale=scale, dims=(B, H, Nq, Nk, D), q_scale=q_scale, ref=_attn_ref64(q, k, v, dO, B, H, Nq, Nk, D, scale))
+
+
+def attention_full_check(inp, strided=False, tag=""):
+    """one forward + backward of the library on prepared inputs, every output against the fp64 reference (case_attention_full)"""
+    B, H, Nq, Nk, D = inp["dims"]
+    q, k, v, dO, scale, ref = inp["q"], inp["k"], inp["v"], inp["dO"], inp["scale"], inp["ref"]
+    dev, HD = q.device, H * D
+    o, lse = K.attn_fwd(q, k, v, B, H, Nq, Nk, D, scale)
+    nan = float("nan")
+    if strided:     # the gradients are column blocks of one buffer (a fused q | k | v projection's dgrad input) with 8 spare columns
+        buf = torch.full((B * max(Nq, Nk), 3 * HD + 8), nan, dtype=f16, device=dev)
+        dq, dk, dv = buf[:B * Nq, :HD], buf[:B * Nk, HD:2 * HD], buf[:B * Nk, 2 * HD:3 * HD]
+    else:
+        dq, dk, dv = (torch.full((n, HD), nan, dtype=f16, device=dev) for n in (B * Nq, B * Nk, B * Nk))
+    K.attn_bwd(q, k, v, o, dO, lse, B, H, Nq, Nk, D, scale, dq, dk, dv)
+    errs = {"o": rel64(o, ref["o"])}
+    # LSE, per row: the kernel rounds q * scale * log2(e) to fp16 once (<= 2^-12 relative per term of the logit); the factor 2 covers
+    # the fp32 accumulation and log2f
+    bound = 2.0 ** -11 * ref["mag"] + 1e-5
+    lse_err = (lse.double() - ref["lse"]).abs()
+    errs["lse"], errs["lse_bound"] = float(lse_err.max()), float(bound.max())
+    errs["lse_margin"] = float((lse_err / bound).max())
+    exact_zero = Nk == 1          # one key: every weight is exactly 1, dq and dk are exactly zero -- no relative error exists
+    for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
+        errs[name] = float(got.double().abs().max()) if (exact_zero and name != "dv") else rel64(got, ref[name])
+    print(f"ATTN_FULL{tag} {inp['dims']} q_scale={inp['q_scale']} strided={strided} " + " ".join(f"{k_}={v_:.2e}" for k_, v_ in errs.items()))
+    assert errs["o"] < 2e-3, ("o", errs)
+    no_outliers(o, ref["o"], "o")
+    assert bool((lse_err <= bound).all()), ("lse", errs)
+    for name, got in (("dq", dq), ("dk", dk), ("dv", dv)):
+        assert bool(torch.isfinite(got.float()).all()), (name, "not every element was written")
+        assert errs[name] < (1e-4 if (exact_zero and name != "dv") else 4e-3), (name, errs)
+        no_outliers(got, ref[name], name)
+    if strided:
+        spare = torch.ones(buf.shape, dtype=torch.bool, device=dev)
+        spare[:B * Nq, :HD] = False
+        spare[:B * Nk, HD:3 * HD] = False
+        assert bool(torch.isnan(buf[spare].float()).all()), "the backward wrote outside its three column blocks"
+    return (o, lse, dq.contiguous(), dk.contiguous(), dv.contiguous()), errs
+
+
+def case_attention_full(dev, B, H, Nq, Nk, D, q_scale=1.0, strided=False):
+    """clora_attn_fwd_f16 + clora_attn_bwd_f16 against fp64 on the same fp16 inputs: o (2e-3) and dq / dk / dv (4e-3) norm-wise and
+    elementwise (no_outliers), the LSE under a per-row bound derived from the one fp16 rounding of the scaled query, every gradient
+    element written (the buffers start as NaN), and with `strided` the gradients as column blocks of one wider buffer whose spare
+    columns must stay untouched.  q_scale > 1: peaked softmax."""
+    return attention_full_check(attention_full_inputs(dev, B, H, Nq, Nk, D, q_scale), strided)
+
+
+ATTN_WIDTHS = [(bw, fw) for bw in (4, 8) for fw in (4, 6, 8, 16)]          # ("attn_bwd_waves", "attn_fwd_waves"); the first is the base
+
+
+def case_attention_widths(dev, B, H, Nq, Nk, D, widths=ATTN_WIDTHS, strided=False):
+    """case_attention_full under every block width of the forward (128 / 192 / 256 / 512 queries) and the backward (128 / 256 queries or
+    keys): each passes the reference checks, and o, lse, dq, dk, dv are bit-identical to the 4-wave results (a block width only changes
+    which workgroup owns which rows)."""
+    inp = attention_full_inputs(dev, B, H, Nq, Nk, D)
+    base = None
+    for bw, fw in widths:
+        with options(attn_bwd_waves=bw, attn_fwd_waves=fw):
+            outs, _ = attention_full_check(inp, strided, tag=f"[bwd {bw} fwd {fw}]")
+        if base is None:
+            base = outs
+        for name, a, b_ in zip(("o", "lse", "dq", "dk", "dv"), base, outs):
+            assert torch.equal(a, b_), f"{name}: bwd {bw} / fwd {fw} waves differ from {widths[0]} in {int((a != b_).sum())} elements"
+
+
+def case_attention_causal(dev, B, H, N, D, strided=True):
+    """clora_attn_fwd_causal_f16 against an fp64 masked softmax (2e-3: the limit of the unmasked forward, same kernel template) and
+    elementwise; row 0 sees one key with weight exactly 1, so it equals v[0] bit for bit; keys and values at positions >= N // 2 are
+    invisible to the rows before them (those rows keep their bits when they change) and visible to the rest.  strided: q | k | v are column blocks of one buffer (the
+    self-attention layout) and the output a column block of a wider NaN-filled one."""
+    g = torch.Generator().manual_seed(57)
+    HD, scale = H * D, D ** -0.5
+    if strided:
+        qkv = rnd((B * N, 3 * HD), dev, g)
+        q, k, v = qkv[:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+        obuf = torch.full((B * N, HD + 16), float("nan"), dtype=f16, device=dev)
+        out = obuf[:, 8:8 + HD]
+    else:
+        q, k, v = (rnd((B * N, HD), dev, g) for _ in range(3))
+        obuf, out = None, torch.full((B * N, HD), float("nan"), dtype=f16, device=dev)
+    o = K.attn_fwd_causal(q, k, v, B, H, N, D, scale, out=out)
+    ref = _attn_ref64(q, k, v, None, B, H, N, N, D, scale, causal=True)["o"]
+    e, worst = rel64(o, ref), float((o.double() - ref).abs().max())
+    print(f"ATTN_CAUSAL {(B, H, N, D)} strided={strided} o={e:.2e} worst={worst:.2e}")
+    assert bool(torch.isfinite(o.float()).all()), "not every output element was written"
+    assert e < 2e-3, e
+    no_outliers(o, ref, "causal o")
+    if strided:
+        assert bool(torch.isnan(obuf[:, :8].float()).all()) and bool(torch.isnan(obuf[:, 8 + HD:].float()).all())
+    o3, v3 = o.reshape(B, N, HD), v.reshape(B, N, HD)
+    assert torch.equal(o3[:, 0], v3[:, 0]), "row 0 attends to key 0 alone"
+    half = N // 2
+    k2, v2 = k.clone().reshape(B, N, HD), v.clone().reshape(B, N, HD)
+    k2[:, half:], v2[:, half:] = rnd((B, N - half, HD), dev, g), rnd((B, N - half, HD), dev, g)
+    o2 = K.attn_fwd_causal(q, k2.reshape(B * N, HD), v2.reshape(B * N, HD), B, H, N, D, scale).reshape(B, N, HD)
+    assert torch.equal(o2[:, :half], o3[:, :half]), "a row changed with keys it must not see"
+    assert bool((o2[:, half:] != o3[:, half:]).any(-1).all()), "a row did not change with keys it sees"
+
+
+def case_attention_causal_rejects(dev, D=72):
+    """head dims above 64 are outside clora_attn_fwd_causal_f16's contract: CLORA_ERR_ARG, nothing launched (the output keeps its bits)"""
+    from controllora_amd import capi
+    g = torch.Generator().manual_seed(58)
+    q, k, v = (rnd((16, D), dev, g) for _ in range(3))
+    out = torch.full((16, D), float("nan"), dtype=f16, device=dev)
+    try:
+        K.attn_fwd_causal(q, k, v, 1, 1, 16, D, D ** -0.5, out=out)
+    except capi.CloraError as e:
+        assert "bad argument" in str(e), e
+    else:
+        raise AssertionError(f"D = {D} was accepted")
+    assert bool(torch.isnan(out.float()).all())
+
+
+def case_groupnorm_offset(dev, B, HW, C, G, offset, silu=False, check=True, eps=1e-5, seed=61):
+    """GroupNorm of unit-variance inputs centred at `offset` (|mean| / std = offset; every other GroupNorm case has 0.2): output and
+    statistics (8e-4) and dx (2e-3) against fp64 under every plan the shape can take ("gn_resident" 0 / 1 x "gn_team" 0 / 2).  The
+    statistics are one pass of fp32 sums over x - P (P: one sample of the group, gn_pivot in clora_norm.hip); plain E[x^2] - mean^2 lost
+    about offset^2 * 2^-24 of the variance and failed this case at offset 100 on the two-launch plan.  check=False: print only."""
+    g = torch.Generator().manual_seed(seed)
+    x = (rnd((B, HW, C), dev, g, dtype=f32) + offset).half()
+    gamma, beta = (1 + 0.2 * rnd((C,), dev, g, dtype=f32)), 0.2 * rnd((C,), dev, g, dtype=f32)
+    dy = rnd((B, HW, C), dev, g)
+    x64 = x.double().clone().requires_grad_(True)
+    y = F.group_norm(x64.permute(0, 2, 1), G, gamma.double(), beta.double(), eps).permute(0, 2, 1)
+    if silu:
+        y = F.silu(y)
+    y.backward(dy.double())
+    xg = x.double().reshape(B, HW, G, C // G)
+    mean = xg.mean((1, 3))
+    rstd = (xg.var((1, 3), unbiased=False) + eps).rsqrt()
+    worst = {}
+    for resident in (0, 1):
+        for team in (0, 2):
+            with options(gn_resident=resident, gn_team=team):
+                out, stats = K.groupnorm_fwd(x, gamma, beta, G, eps, silu)
+                dx, _, _ = K.groupnorm_bwd(x, dy, gamma, beta, stats, G, silu)
+            errs = dict(y=rel64(out, y), mean=rel64(stats[..., 0], mean), rstd=rel64(stats[..., 1], rstd), dx=rel64(dx, x64.grad))
+            print(f"GN_OFFSET {(B, HW, C, G)} offset={offset} silu={silu} gn_resident={resident} gn_team={team} " +
+                  " ".join(f"{k_}={v_:.2e}" for k_, v_ in errs.items()))
+            assert all(math.isfinite(v_) for v_ in errs.values()), errs
+            if check:
+                assert errs["y"] < 8e-4 and errs["mean"] < 8e-4 and errs["rstd"] < 8e-4 and errs["dx"] < 2e-3, (resident, team, errs)
+                no_outliers(out, y, "groupnorm y")
+            for k_, v_ in errs.items():
+                worst[k_] = max(worst.get(k_, 0.0), v_)
+    assert K.gn_team_errors(x.device) == 0
+    return worst
+
+
+def case_lora_down_mode(dev, mode, M, Kd):
+    """option "lora_down_mode": three stacked rank-4 down-projections with a second input on the first, against fp32 torch (1e-5: fp32
+    summation-order noise) and elementwise; two launches in one mode give the same bits"""
+    g = torch.Generator().manual_seed(61)
+    X, X2 = rnd((M, Kd), dev, g), rnd((M, Kd), dev, g)
+    D = rnd((12, Kd), dev, g, 0.25, dtype=f32)
+    ref = X.float() @ D.T
+    ref[:, :4] += X2.float() @ D[:4].T
+    try:
+        K.set_option("lora_down_mode", mode)
+        T = torch.empty((M, 12), dtype=f32, device=dev)
+        K.lora_down_multi([K.down_job(X, D, T, 0, M, Kd, X2=X2, r2=4)])
+        again = torch.empty_like(T)
+        K.lora_down_multi([K.down_job(X, D, again, 0, M, Kd, X2=X2, r2=4)])
+    finally:
+        K.set_option("lora_down_mode", 1)                   # the library default
+    assert rel(T, ref) < 1e-5 and torch.equal(T, again), (mode, M, Kd, rel(T, ref))
+    no_outliers(T, ref, f"lora_down mode {mode} M={M} K={Kd}")
+
+
+# ---- the option table (include/clora.h above clora_set_option): a launch set per knob, run at the default and at another value
+def _launches_epilogue(dev, big):
+    """the projection epilogues on the 8-wave tiles 51..58.  Each entry: (label, output, fp64-derived reference, rel limit, exact) --
+    exact: the header promises the same bits at every setting of "epi_hoist" / "epi_two_phase" for this launch"""
+    from controllora_amd import ops
+    g = torch.Generator().manual_seed(91)
+    M, N, K_ = (4100, 320, 320) if big else (300, 320, 128)
+    A, B = rnd((M, K_), dev, g), rnd((N, K_), dev, g, 1 / math.sqrt(K_))
+    bias, res, rowadd = rnd((N,), dev, g, dtype=f32), rnd((M, N), dev, g), rnd((4, N), dev, g)
+    T, U, Ut = rnd((M, 8), dev, g, dtype=f32), rnd((N, 4), dev, g, dtype=f32), rnd((4, N), dev, g, dtype=f32)
+    base = A.double() @ B.double().T
+    seg = torch.arange(N, device=dev) // (N // 2)
+    lora = torch.stack([T[:, :4].double() @ U[n].double() if int(s_) == 0 else T[:, 4:].double() @ U[n].double() for n, s_ in enumerate(seg.tolist())], 1)
+    fin = lambda pre: pre.float().half().float() + res.float()           # the epilogue rounds once, then adds the residual
+    out = []
+    for tile in range(51, 59):
+        kw = dict(tile_cfg=tile, split_k=1, _tuned=False)
+        out.append((f"tile {tile} bias+adapter(2 segments)+residual",
+                    K.gemm(A, B, M, N, K_, bias=bias, residual=res, lora_t=T, lora_u=U, lora_seg=N // 2, lora_scale=0.7, **kw),
+                    fin(base + bias.double() + 0.7 * lora), 6e-4, False))
+        T4 = T[:, :4].contiguous()
+        out.append((f"tile {tile} adapter(lora_u_tr)+residual",
+                    K.gemm(A, B, M, N, K_, residual=res, lora_t=T4, lora_u=Ut, lora_seg=N, lora_u_tr=True, lora_r=4, **kw),
+                    fin(base + T4.double() @ Ut.double()), 6e-4, False))
+        out.append((f"tile {tile} bias+residual", K.gemm(A, B, M, N, K_, bias=bias, residual=res, **kw), fin(base + bias.double()), 6e-4, True))
+        kw["split_k"] = 2
+        out.append((f"tile {tile} split-K 2 bias+rowadd+adapter+residual",
+                    K.gemm(A, B, M, N, K_, bias=bias, rowadd=rowadd, rows_per_batch=M // 4, residual=res, lora_t=T, lora_u=U, lora_seg=N // 2,
+                           lora_scale=0.7, **kw),
+                    fin(base + bias.double() + rowadd.double().repeat_interleave(M // 4, 0) + 0.7 * lora), 6e-4, False))
+    Dm = rnd((4, K_), dev, g, 1 / math.sqrt(K_), dtype=f32)                # the adapter's down-projection evaluated inside the launch
+    pack = ops.ADAPTER_PACKS.get([Dm])
+    T_ref = A.double() @ Dm.double().T
+    for tile in (55, 0):
+        Tw = torch.full((M, 4), float("nan"), dtype=f32, device=dev)
+        y = K.gemm(A, B, M, N, K_, bias=bias, residual=res, lora_t=Tw, lora_u=U, lora_seg=N, lora_scale=0.7, lora_r=4, lora_dpack=pack,
+                   tile_cfg=tile, split_k=1, _tuned=False)
+        out.append((f"tile {tile} lora_dpack y", y, fin(base + bias.double() + 0.7 * (T_ref @ U.double().T)), 6e-4, True))
+        out.append((f"tile {tile} lora_dpack T", Tw, T_ref, 2e-6, True))
+    return out
+
+
+def _launches_groupnorm(dev, big):
+    """forward and backward under "gn_resident" 0 and 1.  exact (the same bits at every "gn_blocks"): the one-launch plans, which do
+    not chunk rows -- `one_launch` shapes under gn_resident 1, team shapes always; the two-launch scheme re-partitions its fp32 sums"""
+    shapes = [(2, 300, 320, 32, "one_launch"), (2, 64, 1280, 32, "one_launch"), (1, 1100, 64, 8, "any")]
+    if big:
+        shapes = [(4, 256, 1280, 32, "one_launch"), (4, 4096, 320, 32, "team"), (3, 1000, 640, 32, "any"), (2, 300, 320, 32, "one_launch")]
+    out = []
+    for B, HW, C, G, kind in shapes:
+        g = torch.Generator().manual_seed(HW + C)
+        x = (rnd((B, HW, C), dev, g).float() * 1.5 + 0.3).half()
+        gamma, beta = (1 + 0.2 * rnd((C,), dev, g, dtype=f32)), 0.2 * rnd((C,), dev, g, dtype=f32)
+        dy, dres = rnd((B, HW, C), dev, g), rnd((B, HW, C), dev, g)
+        x64 = x.double().clone().requires_grad_(True)
+        y = F.silu(F.group_norm(x64.permute(0, 2, 1), G, gamma.double(), beta.double(), 1e-5).permute(0, 2, 1))
+        y.backward(dy.double())
+        for resident in (0, 1):
+            with options(gn_resident=resident):
+                o, st = K.groupnorm_fwd(x, gamma, beta, G, 1e-5, True)
+                dx, _, _ = K.groupnorm_bwd(x, dy, gamma, beta, st, G, True, dres=dres)
+            exact = kind == "team" or (kind == "one_launch" and resident == 1)
+            tag = f"{(B, HW, C, G)} gn_resident {resident}"
+            out += [(f"{tag} y", o, y.detach(), 8e-4, exact, 2e-4), (f"{tag} stats", st, None, None, exact, 1e-5),
+                    (f"{tag} dx", dx, x64.grad + dres.double(), 2e-3, exact, 3e-4)]
+    return out
+
+
+def _launches_strip(dev, big):
+    """the strip convolution (tile_cfg 61), forward + bias and dgrad, on maps tall enough for the block count to change the row ranges"""
+    import ctypes
+    from controllora_amd import capi
+    out = []
+    for Bn, H, W, Ci, Co in ([(4, 512, 512, 32, 32), (2, 256, 256, 32, 64)] if big else [(1, 40, 128, 32, 32), (2, 24, 128, 32, 64)]):
+        g = torch.Generator().manual_seed(H + Co)
+        x, w = rnd((Bn, Ci, H, W), dev, g), rnd((Co, Ci, 3, 3), dev, g, 1 / math.sqrt(9 * Ci))
+        bias, dy = rnd((Co,), dev, g, dtype=f32), rnd((Bn, Co, H, W), dev, g)
+        xin = x.float().clone().requires_grad_(True)               # fp32 torch, as in case_conv_strip (K = 288 / 576 products)
+        y = F.conv2d(xin, w.float(), bias.float(), padding=1)
+        y.backward(dy.float())
+        M = Bn * H * W
+        xn = x.permute(0, 2, 3, 1).contiguous().reshape(M, Ci)
+        wp = w.permute(0, 2, 3, 1).contiguous().reshape(Co, 9 * Ci)
+        cd, _, _ = K.conv_fwd_desc(H, W, Ci, 3, 1, 1)
+        assert capi.lib().cdll.clora_conv_strip_eligible(M, Co, ctypes.byref(cd)) == 1
+        out.append((f"strip fwd {(Bn, H, W, Ci, Co)}", K.gemm(xn, wp, M, Co, 9 * Ci, conv=cd, bias=bias),
+                    y.detach().permute(0, 2, 3, 1).reshape(M, Co), 6e-4, True))
+        wd = w.permute(1, 2, 3, 0).contiguous().reshape(Ci, 9 * Co)
+        dyn = dy.permute(0, 2, 3, 1).contiguous().reshape(M, Co)
+        cdd = K.conv_dgrad_desc(H, W, Co, H, W, 3, 1, 1)
+        if capi.lib().cdll.clora_conv_strip_eligible(M, Ci, ctypes.byref(cdd)) == 1:
+            out.append((f"strip dgrad {(Bn, H, W, Ci, Co)}", K.gemm(dyn, wd, M, Ci, 9 * Co, conv=cdd),
+                        xin.grad.permute(0, 2, 3, 1).reshape(M, Ci), 6e-4, True))
+    assert len(out) >= 3, "no shape took the strip dgrad"
+    return out
+
+
+def _launches_wgrad_patch(dev, big):
+    """case_conv_wgrad_patch's inputs: dW and db of the patch-staged weight-gradient kernel (fp32 atomics: 2e-5 across block counts)"""
+    out = []
+    for Bn, H, W, Ci, Co, stride in ([(4, 256, 256, 32, 64, 1), (4, 512, 512, 32, 32, 2)] if big else [(2, 5, 64, 32, 64, 1), (1, 6, 128, 32, 32, 2)]):
+        g = torch.Generator().manual_seed(21)
+        x, w = rnd((Bn, Ci, H, W), dev, g), rnd((Co, Ci, 3, 3), dev, g, 1 / math.sqrt(9 * Ci))
+        Ho, Wo = (H, W) if stride == 1 else (H // 2, W // 2)
+        dy = rnd((Bn, Co, Ho, Wo), dev, g)
+        w32 = w.float().clone().requires_grad_(True)               # fp32 torch autograd, as in case_conv_wgrad_patch
+        (F.conv2d(x.float(), w32, padding=1) if stride == 1 else F.conv2d(F.pad(x.float(), (0, 1, 0, 1)), w32, stride=2)).backward(dy.float())
+        xn = x.permute(0, 2, 3, 1).contiguous().reshape(-1, Ci)
+        dyn = dy.permute(0, 2, 3, 1).contiguous().reshape(-1, Co)
+        cd, _, _ = K.conv_fwd_desc(H, W, Ci, 3, stride, 1 if stride == 1 else 0, asym_pad=stride == 2)
+        dW, db = K.conv_wgrad(dyn, xn, Bn * Ho * Wo, Co, 9 * Ci, cd, with_bias=True)
+        tag = f"wgrad {(Bn, H, W, Ci, Co)} stride {stride}"
+        out += [(f"{tag} dW", dW, w32.grad.permute(0, 2, 3, 1).reshape(Co, 9 * Ci), 1e-4, False, 2e-5),
+                (f"{tag} db", db, dy.float().sum((0, 2, 3)), 1e-4, False, 2e-5)]
+    return out
+
+
+# knob -> (launch set, limit across settings for the launches that are not `exact` (0.0: the same bits on every launch; None: the
+# launch's own sixth element), repeat launches give the same bits)
+_OPTION_SETS = {"epi_hoist": (_launches_epilogue, 2e-5, True), "epi_two_phase": (_launches_epilogue, 0.0, True),
+                "gn_unroll": (_launches_groupnorm, 0.0, True), "gn_blocks": (_launches_groupnorm, None, True),
+                "strip_blocks": (_launches_strip, 0.0, True), "wgrad_patch": (_launches_wgrad_patch, None, False)}
+
+
+def case_option_invariance(dev, name, value, big=None):
+    """One row of the option table: the knob's launch set at the default and at `value` -- both agree with the fp64 reference (fp32 torch for
+    the convolutions, as in their own cases) inside the family's limits, repeat launches give the same bits at either setting (except the kernels that use atomics), and across the two
+    settings the results are bit-identical wherever include/clora.h promises it and inside the stated limit elsewhere:
+      "epi_hoist"    orders the four products of the rank-4 adapter term differently: 2e-5 (case_gemm_fused_down) on adapter launches,
+                     same bits on launches without an adapter and with lora_dpack (those always hoist);
+      "gn_blocks"    re-partitions the fp32 sums of the two-launch GroupNorm plan: 2e-4 / 1e-5 / 3e-4 for y / statistics / dx
+                     (case_groupnorm), same bits on the one-launch plans;
+      "wgrad_patch"  fp32 atomics in another order: 2e-5 (case_conv_wgrad_patch);
+      "epi_two_phase", "gn_unroll", "strip_blocks": same bits everywhere."""
+    launches, across, stable = _OPTION_SETS[name]
+    big = (dev != "cpu") if big is None else big
+    assert value != option_default(name)
+    runs = {}
+    for setting in (option_default(name), value):
+        with options(**{name: setting}):
+            runs[setting] = launches(dev, big)
+            again = launches(dev, big) if stable else None
+        for i, (label, got, ref, lim, *_) in enumerate(runs[setting]):
+            if ref is not None:
+                e = rel64(got, ref)
+                assert e < lim, (name, setting, label, e)
+                if lim > 1e-4:
+                    no_outliers(got, ref, label)
+            if again is not None:
+                assert torch.equal(got, again[i][1]), (name, setting, label, "two identical launches differ")
+    changed = []
+    for (label, a, _, _, exact, *own), (_, b_, *_rest) in zip(runs[option_default(name)], runs[value]):
+        if torch.equal(a, b_):
+            continue
+        e = rel64(b_, a)
+        changed.append((label, e))
+        lim = 0.0 if exact else (across if across is not None else own[0])   # a knob's own promise (0.0: same bits) beats the launch's
+        assert e < lim, (name, value, label, f"differs by {e:.2e} across settings (limit {lim:.0e})")
+    print(f"OPTION {name}={value} vs {option_default(name)}: {len(runs[value])} launches, bits changed in {len(changed)}" +
+          (f", worst {max(changed, key=lambda c: c[1])}" if changed else ""))
+    return changed
