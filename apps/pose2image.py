@@ -65,7 +65,8 @@ def main(argv=None):
     ap.add_argument("--a_prompt", default="best quality, extremely detailed")
     ap.add_argument("--n_prompt", default="longbody, lowres, bad anatomy, bad hands, missing fingers, extra digit, fewer digits, cropped, worst quality, low quality")
     ap.add_argument("--num_samples", type=int, default=1)
-    ap.add_argument("--image_resolution", type=int, default=512)
+    ap.add_argument("--image_resolution", type=int, default=512,
+                    help="short side of the generated image; the reference slider runs 256 ... 768, both sides become multiples of 64")
     ap.add_argument("--detect_resolution", type=int, default=512)
     ap.add_argument("--sample_steps", type=int, default=30)
     ap.add_argument("--scale", type=float, default=9.0)

@@ -130,6 +130,7 @@ _PROTOS = {
     "clora_conv_weight_pack_multi_f32": [C.POINTER(ConvPackJob), _I, _P],
     "clora_conv_wgrad_unpack_multi_f32": [C.POINTER(ConvUnpackJob), _I, _P],
     "clora_attn_fwd_f16": [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P],
+    "clora_attn_max_head_dim": [_I],
     "clora_attn_fwd_causal_f16": [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P],
     "clora_attn_bwd_f16": [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F, _P, _Z, _P],
     "clora_groupnorm_fwd_f16": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _Z, _P],

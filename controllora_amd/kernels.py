@@ -452,8 +452,15 @@ def softmax_rows(x: torch.Tensor, scale: float = 1.0, out: Optional[torch.Tensor
     return y
 
 
+def attn_max_head_dim(backward: bool = False) -> int:
+    """the largest head dim attn_fwd (512) / attn_bwd (160) accept (clora_attn_max_head_dim: host-only, nothing is launched)"""
+    return int(capi.lib().cdll.clora_attn_max_head_dim(1 if backward else 0))
+
+
 def attn_fwd(q, k, v, B, H, Nq, Nk, D, scale, out=None):
-    """q/k/v: 2-D row-strided views [B*N, >=H*D] (stride(0) is the row pitch)."""
+    """q/k/v: 2-D row-strided views [B*N, >=H*D] (stride(0) is the row pitch, a multiple of 8).  D % 8 == 0 and
+    D <= attn_max_head_dim() = 512: head dims above 160 run the forward-only wide kernel (the VAE's single 512-channel head),
+    so only an `lse` of D <= attn_max_head_dim(True) = 160 can go on to attn_bwd.  Anything else raises CloraError, nothing is launched."""
     o = out if out is not None else torch.empty((B * Nq, H * D), dtype=f16, device=q.device)
     lse = torch.empty((B, H, Nq), dtype=f32, device=q.device)
     _call("clora_attn_fwd_f16", ptr(q, f16), q.stride(0), ptr(k, f16), k.stride(0), ptr(v, f16), v.stride(0),

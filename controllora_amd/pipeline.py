@@ -111,7 +111,8 @@ class ControlLoRAPipeline:
     def __call__(self, prompt, guide, a_prompt="", n_prompt="", num_samples=1, ddim_steps=50, scale=9.0, seed=None,
                  output_type="uint8", sampler="ddim"):
         """guide: float tensor [1, 3, H, W] (broadcast over the samples) or [num_samples, 3, H, W] (one guide per image), in
-        [-1, 1]; H, W multiples of 64"""
+        [-1, 1]; H, W multiples of 64, square or not -- every size the reference apps' image_resolution slider gives (256 ... 768):
+        the UNet's and the VAE's attention are flash kernels that take any number of tokens"""
         dev = next(self.text_encoder.parameters()).device
         gen = torch.Generator(device=dev)
         if seed is not None:

@@ -4,9 +4,10 @@
 (apps/gradio_canny2image.py:88-92).  Same state-dict keys as upstream `AutoencoderKL` (diffusers >= 0.13:
 encoder/decoder `.down_blocks/.up_blocks.{i}.resnets.{j}`, `.mid_block.attentions.0.{group_norm,query,key,value,
 proj_attn}`, `quant_conv`, `post_quant_conv`), NHWC fp16 activations, every conv an implicit GEMM with the
-bias / residual fused, GroupNorm+SiLU fused.  The single-head d=512 mid-block attention materialises its
-scores with the GEMM kernel (head dim is beyond the flash kernels) and normalises them with
-clora_softmax_rows_f16; the value bias is applied after P.V (softmax rows sum to 1).
+bias / residual fused, GroupNorm+SiLU fused.  The single-head d=512 mid-block attention is one launch of the wide
+flash forward kernel (clora_attn_wide.hip) for the whole batch wherever the materialised scores cannot run (more than 8,192
+latent tokens: 768 x 768 is 9,216), so any image size whose sides are multiples of 8 encodes and decodes; below that
+VaeAttention.use_flash picks between the two paths (see there for the default).
 Oracle: oracle/vae_ref.py (restated from the published diffusers algorithm -- parity unpinned, see there).
 """
 from __future__ import annotations
@@ -45,6 +46,17 @@ class VaeResnet(nn.Module):
 
 
 class VaeAttention(nn.Module):
+    """One head of `c` channels over all N tokens of an image.  Flash path: q, k, v from the three projections (the value bias in
+    the projection), ONE K.attn_fwd launch for the whole batch (the wide forward kernel at c > 160), no scores buffer: any N.
+    Scores path: the N x N scores of one image at a time through the GEMM kernel and clora_softmax_rows_f16, which keeps a row in
+    registers and stops at SCORES_MAX_TOKENS columns; it serves c > K.attn_max_head_dim() and is the A/B partner of the flash path
+    (tools/vae_bench.py --attn flash|scores sets `use_flash`; more tokens than the scores path can take run the flash path regardless).
+    `use_flash` is False, i.e. up to SCORES_MAX_TOKENS tokens keep the path and the bits they had: the flash path becomes the default
+    there once tools/vae_bench.py has shown encode and decode at 4 x 512^2 no slower than the scores path by more than that path's own
+    spread, and that run has not been made yet (README.md)."""
+    use_flash = False
+    SCORES_MAX_TOKENS = 8192
+
     def __init__(self, c, groups):
         super().__init__()
         self.group_norm = GroupNorm(groups, c, 1e-6)
@@ -52,20 +64,31 @@ class VaeAttention(nn.Module):
 
     def forward(self, x):
         B, N, C_ = x.shape
-        h = self.group_norm(x, False)
+        max_d = K.attn_max_head_dim()
+        flash = C_ <= max_d and (self.use_flash or N > self.SCORES_MAX_TOKENS)
+        if not flash and N > self.SCORES_MAX_TOKENS:
+            raise ValueError(f"VaeAttention: {N} tokens of {C_} channels fit neither path: the flash kernels take head dims up to "
+                             f"{max_d}, the materialised scores up to {self.SCORES_MAX_TOKENS} tokens")
         x2 = x.reshape(B * N, C_)
-        hq = self.query(h.reshape(B * N, C_))
-        hk = self.key(h.reshape(B * N, C_))
+        h = self.group_norm(x, False).reshape(B * N, C_)
+        if flash:
+            out, _ = K.attn_fwd(self.query(h), self.key(h), self.value(h), B, 1, N, N, C_, 1.0 / math.sqrt(C_))
+        else:
+            out = self._scores_attention(h, B, N, C_)
+        return self.proj_attn(out, residual=x2).reshape(B, N, C_)
+
+    def _scores_attention(self, h, B, N, C_):
+        hq, hk = self.query(h), self.key(h)
         vp = self.value.pack()
-        out = torch.empty_like(x2)
-        scores = torch.empty((N, N), dtype=f16, device=x.device)
+        out = torch.empty_like(h)
+        scores = torch.empty((N, N), dtype=f16, device=h.device)
         for b in range(B):
-            q, k, hb = hq[b * N:(b + 1) * N], hk[b * N:(b + 1) * N], h[b]
+            q, k, hb = hq[b * N:(b + 1) * N], hk[b * N:(b + 1) * N], h[b * N:(b + 1) * N]
             K.gemm(q, k, N, N, C_, out=scores)                        # q k^T; the (C^-1/4)^2 scale goes into softmax
             K.softmax_rows(scores, 1.0 / math.sqrt(C_), out=scores)
             vt = K.gemm(vp.w, hb, C_, N, C_)                          # V^T = Wv h^T  [C, N]  (bias added after P.V)
             K.gemm(scores, vt, N, C_, N, bias=vp.bias, out=out[b * N:(b + 1) * N])
-        return self.proj_attn(out, residual=x2).reshape(B, N, C_)
+        return out
 
 
 class _VaeBlock(nn.Module):

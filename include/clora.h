@@ -302,16 +302,24 @@ int clora_conv_wgrad_unpack_multi_f32(const clora_conv_unpack_job_t* jobs, int n
 /* ---- attention core: O = softmax(Q K^T * scale) V per (batch, head), flash-style (never
  * materialises the [B*H, N, Nk] scores the reference builds at models.py:140-141, 270-271).
  * q: [B, Nq, H*D] with row stride ldq (elements), k/v: [B, Nk, H*D] strides ldk/ldv, o: ldo.
- * lse: [B, H, Nq] fp32 (natural-log sum-exp of scaled scores), needed by the backward. */
+ * lse: [B, H, Nq] fp32 (natural-log sum-exp of scaled scores), needed by the backward; may be NULL.
+ * Head dims: D % 8 == 0 and D <= 512.  D <= 160 runs the kernels the backward pairs with; 160 < D <= 512 runs one forward-only kernel
+ * padded to 512 (clora_attn_wide.hip: the single 512-channel head of the VAE's mid-block attention, any number of tokens).  Anything
+ * else returns CLORA_ERR_ARG with nothing launched.  No workspace, no atomics; repeat launches are bit-identical. */
 int clora_attn_fwd_f16(const clora_half* q, int ldq, const clora_half* k, int ldk, const clora_half* v, int ldv,
                        clora_half* o, int ldo, float* lse, int B, int H, int Nq, int Nk, int D, float scale,
                        void* stream);
-/* Forward only, causal: key j is visible to query i iff j <= i (self-attention, Nq = Nk = N, head dims <= 64).  The masked
+/* The largest head dim the forward (backward == 0: 512) or the backward (backward != 0: 160) accepts.  Host-only, nothing is
+ * launched: a caller picks its path without provoking CLORA_ERR_ARG. */
+int clora_attn_max_head_dim(int backward);
+/* Forward only, causal: key j is visible to query i iff j <= i (self-attention, Nq = Nk = N, head dims <= 64 -- the wide forward
+ * kernel has no causal form).  The masked
  * self-attention of the frozen CLIP text encoder (reference train_text_to_image_control_lora.py:768
  * `text_encoder(batch["input_ids"])[0]`; transformers CLIPTextTransformer builds the same mask additively). */
 int clora_attn_fwd_causal_f16(const clora_half* q, int ldq, const clora_half* k, int ldk, const clora_half* v, int ldv,
                               clora_half* o, int ldo, int B, int H, int N, int D, float scale, void* stream);
-/* dq/dk/dv given do (autograd of the same lines). delta: [B,H,Nq] fp32 scratch.  workspace (optional, one
+/* dq/dk/dv given do (autograd of the same lines); head dims <= 160 (clora_attn_max_head_dim(1): there is no backward for the wide
+ * forward kernel, D > 160 returns CLORA_ERR_ARG). delta: [B,H,Nq] fp32 scratch.  workspace (optional, one
  * 2*B*Nk*H*D*4-byte slab pair per query split, up to 16) lets the dK/dV kernel split its query loop when there are few keys
  * (cross-attention); the splits are folded in a fixed order (no atomics). */
 int clora_attn_bwd_f16(const clora_half* q, int ldq, const clora_half* k, int ldk, const clora_half* v, int ldv,
