@@ -138,6 +138,8 @@ _PROTOS = {
     "clora_groupnorm_fwd_f16_ex": [_P, _P, _I, C.POINTER(Deferred), _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _Z, _P],
     "clora_groupnorm_bwd_f16_ex": [_P, _P, C.POINTER(Deferred), _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P],
     "clora_groupnorm_fwd_f16_team": [_P, _P, _I, C.POINTER(Deferred), _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _Z, _P, _Z, _P],
+    "clora_groupnorm_fwd_f16_lo": [_P, _P, _I, C.POINTER(Deferred), _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _Z, _P, _Z, _P, _P, _P],
+    "clora_layernorm_fwd_f16_lo": [_P, _P, _P, _P, _I, _I, _F, _P, _P],
     "clora_groupnorm_bwd_f16_team": [_P, _P, C.POINTER(Deferred), _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _Z, _P],
     "clora_layernorm_bwd_f16_ex": [_P, _P, C.POINTER(Deferred), _P, _P, _P, _I, _I, _F, _P],
     "clora_finish_deferred": [C.POINTER(Deferred), _P],

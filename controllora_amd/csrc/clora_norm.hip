@@ -52,6 +52,10 @@ struct GnArgs {
     int tm_nb, tm_rpb;             // members per unit, rows per member
     int tm_probe;                  // emulator only (blocks run one after the other): publish, do not gather
     unsigned tm_spin;
+    // compensated trunk (include/clora.h clora_groupnorm_fwd_f16_lo), fwd kernels instantiated with LO only.  Appended: the kernel
+    // argument offsets of every field above, and so the code of the instantiations without LO, are unchanged.
+    const half_t* x_lo;   // rounding remainder of x, layout and pitch of x (nullptr: none)
+    const half_t* x2_lo;  // rounding remainder of x2, layout and pitch of x2 (nullptr: none)
 };
 
 constexpr int kTeamUnits = 32, kTeamMembers = 256, kTeamGran = 64, kTeamBlocks = 256, kTeamNT = 512;
@@ -66,6 +70,22 @@ __device__ __forceinline__ GnCol gn_in_col(const GnArgs& a, int ch0) {
     if (a.x2 && ch0 >= a.Ca) { c.p = a.x2 + (ch0 - a.Ca); c.pitch = a.C - a.Ca; }
     else { c.p = a.x + ch0; c.pitch = a.x2 ? a.Ca : a.C; }
     return c;
+}
+// LO kernels: the remainder of the same chunk (pitch = that of the hi column).  A half without a remainder re-reads hi (a valid
+// address: the loads stay unconditional) with the weight m = 0, so v = float(hi) + m * float(lo) is float(hi) exactly for finite hi.
+// Cost of that form: the half without a remainder is loaded twice (the second load hits the cache line the first one brought in, but
+// it is a second load instruction per chunk), and an infinite hi gives 0 * inf = NaN where the plain kernels give inf.
+struct GnLoCol { const half_t* p; float m; };
+__device__ __forceinline__ GnLoCol gn_lo_col(const GnArgs& a, int ch0, const GnCol& hi) {
+    const half_t* lo = (a.x2 && ch0 >= a.Ca) ? (a.x2_lo ? a.x2_lo + (ch0 - a.Ca) : nullptr) : (a.x_lo ? a.x_lo + ch0 : nullptr);
+    GnLoCol c;
+    c.p = lo ? lo : hi.p; c.m = lo ? 1.0f : 0.0f;
+    return c;
+}
+// the value a LO kernel normalises: float(hi) + float(lo), formed once per element where it is loaded
+__device__ __forceinline__ void gn_val8(const half8& hi, const half8& lo, float m, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (float)hi[e] + m * (float)lo[e];
 }
 struct GnColW { half_t* p; int pitch; };
 __device__ __forceinline__ GnColW gn_dx_col(const GnArgs& a, int ch0) {
@@ -153,7 +173,7 @@ __device__ __forceinline__ void gn_block_reduce(float* red, const float (&a)[NJ]
 constexpr int kRedFloats = 2 * 4096;   // LDS: max(nrl*C, C) * 2 floats with nrl*C <= 2048 for CH < 256
 
 // ---- forward, pass 1
-template <int NJ, int UF = 1>
+template <int NJ, int UF = 1, bool LO = false>
 __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
     constexpr int kGnU = ::kGnU * UF;                        // rows loaded before the first is used (option "gn_unroll": UF = 2)
     __shared__ float red[kRedFloats];
@@ -176,15 +196,23 @@ __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
         float piv[NJ][8];                                        // see gn_pivot
 #pragma unroll
         for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; gn_pivots8(p, b, cb + (cc < CH ? cc : c0) * 8, p.C / p.G, piv[j]); }
+        GnLoCol lcol[NJ];
+        if constexpr (LO) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; lcol[j] = gn_lo_col(p, cb + (cc < CH ? cc : c0) * 8, col[j]); }
+        }
         const size_t brow = (size_t)b * p.HW;
         for (int it0 = 0; it0 < nit; it0 += kGnU) {
-            half8 v[kGnU][NJ];
+            half8 v[kGnU][NJ], w[LO ? kGnU : 1][NJ];
 #pragma unroll
             for (int u = 0; u < kGnU; ++u) {                     // every load of the batch first ...
                 const int r = r_beg + rl + (it0 + u) * nrl;
                 const size_t row = brow + (size_t)(r < r_end ? r : r_beg);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j) v[u][j] = ld8(col[j].p + row * col[j].pitch);
+                for (int j = 0; j < NJ; ++j) {
+                    v[u][j] = ld8(col[j].p + row * col[j].pitch);
+                    if constexpr (LO) w[u][j] = ld8(lcol[j].p + row * col[j].pitch);
+                }
             }
 #pragma unroll
             for (int u = 0; u < kGnU; ++u) {                     // ... then the sums, rows past the chunk masked to zero
@@ -192,6 +220,15 @@ __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     CLORA_KEEP(v[u][j]);
+                    if constexpr (LO) {
+                        CLORA_KEEP(w[u][j]);
+                        if (c0 + j * cstep < CH) {
+                            float xv[8];
+                            gn_val8(v[u][j], w[u][j], lcol[j].m, xv);
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
+                        }
+                    } else
                     if (c0 + j * cstep < CH) {                   // thread-constant
 #pragma unroll
                         for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[u][j][e] - piv[j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
@@ -298,7 +335,7 @@ __device__ __forceinline__ void gn_fold_groups(const GnArgs& p, int b, int t, fl
     if (g < p.G && part == 0) { out2[g * 2] = s * inv_n; out2[g * 2 + 1] = q * inv_n; }
 }
 
-template <int NJ, int UF = 1>
+template <int NJ, int UF = 1, bool LO = false>
 __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
     constexpr int kGnU = ::kGnU * UF;
     __shared__ float mr[64 * 2];
@@ -336,15 +373,23 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
     GnCol col[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; col[j] = gn_in_col(p, cb + (cc < CH ? cc : c0) * 8); }
+    GnLoCol lcol[NJ];
+    if constexpr (LO) {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { const int cc = c0 + j * cstep; lcol[j] = gn_lo_col(p, cb + (cc < CH ? cc : c0) * 8, col[j]); }
+    }
     const size_t brow = (size_t)b * p.HW;
     for (int it0 = 0; it0 < nit; it0 += kGnU) {
-        half8 v[kGnU][NJ];
+        half8 v[kGnU][NJ], w[LO ? kGnU : 1][NJ];
 #pragma unroll
         for (int u = 0; u < kGnU; ++u) {
             const int r = r_beg + rl + (it0 + u) * nrl;
             const size_t row = brow + (size_t)(r < r_end ? r : r_beg);
 #pragma unroll
-            for (int j = 0; j < NJ; ++j) v[u][j] = ld8(col[j].p + row * col[j].pitch);
+            for (int j = 0; j < NJ; ++j) {
+                v[u][j] = ld8(col[j].p + row * col[j].pitch);
+                if constexpr (LO) w[u][j] = ld8(lcol[j].p + row * col[j].pitch);
+            }
         }
 #pragma unroll
         for (int u = 0; u < kGnU; ++u) {
@@ -354,10 +399,12 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
             for (int j = 0; j < NJ; ++j) {
                 const int cc = c0 + j * cstep;
                 CLORA_KEEP(v[u][j]);
+                float xv[8];
+                if constexpr (LO) { CLORA_KEEP(w[u][j]); gn_val8(v[u][j], w[u][j], lcol[j].m, xv); }
                 half8 o;                                         // computed unconditionally (keeps the loads above the branch) ...
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    float yv = (float)v[u][j][e] * sc[j][e] + sh[j][e];
+                    float yv = (LO ? xv[e] : (float)v[u][j][e]) * sc[j][e] + sh[j][e];
                     if (p.fuse_silu) yv = silu_f(yv);
                     o[e] = (half_t)yv;
                 }
@@ -537,8 +584,10 @@ __device__ __forceinline__ void gn_res_reduce(float* red, float* chs, const floa
 
 // DEF: x is a deferred split-K GEMM (GnArgs.fin_*): every chunk is folded from the slabs with the GEMM's own epilogue while it is
 // loaded (finish_chunk8: the bits the finish kernel would have stored) and written back once through xcopy.
-template <int NT, int NPT, bool DEF = false>
+// LO (never with DEF): the rows' remainders stay in registers next to the rows
+template <int NT, int NPT, bool DEF = false, bool LO = false>
 __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
+    static_assert(!(DEF && LO), "a launch that writes a remainder is never deferred");
     __shared__ float red[NT * 16];                               // [nrl][CS][2] with nrl * CS <= NT * 8
     __shared__ float chs[256 * 8 * 2];                           // per-channel totals of the slab (CS <= 2048)
     __shared__ float mr[64 * 2];
@@ -555,7 +604,9 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
     const floatx4* gp = reinterpret_cast<const floatx4*>(p.gamma + cb + c0 * 8);
     const floatx4* bp = reinterpret_cast<const floatx4*>(p.beta + cb + c0 * 8);
     const floatx4 ga = gp[0], gb = gp[1], ba = bp[0], bb = bp[1];
-    half8 v[NPT];
+    half8 v[NPT], w[LO ? NPT : 1];
+    GnLoCol lcol = {nullptr, 0.f};
+    if constexpr (LO) lcol = gn_lo_col(p, cb + (active ? c0 : 0) * 8, col);
     float s[8], q[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
@@ -568,6 +619,7 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
                 if (k < npt) v[k] = finish_chunk8(p.fin_partial, p.fin_splits, p.B * p.HW, p.C, p.fin_epi, (int)(brow + (r < p.HW ? r : 0)), cb + c0 * 8);
             } else {
                 v[k] = (k < npt) ? ld8(col.p + (brow + (size_t)(r < p.HW ? r : 0)) * col.pitch) : zero8();
+                if constexpr (LO) w[k] = (k < npt) ? ld8(lcol.p + (brow + (size_t)(r < p.HW ? r : 0)) * col.pitch) : zero8();
             }
         }
     }
@@ -586,8 +638,15 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = k < npt && rl + k * nrl < p.HW;
+            if constexpr (LO) {
+                float xv[8];
+                gn_val8(v[k], w[k], lcol.m, xv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
+            } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
+            }
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f / ((float)p.HW * (float)cpg));
@@ -614,10 +673,12 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const int r = rl + k * nrl;
+        float xv[8];
+        if constexpr (LO) gn_val8(v[k], w[k], lcol.m, xv);
         half8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float yv = (float)v[k][e] * sc[e] + sh[e];
+            float yv = (LO ? xv[e] : (float)v[k][e]) * sc[e] + sh[e];
             if (p.fuse_silu) yv = silu_f(yv);
             o[e] = (half_t)yv;
         }
@@ -768,7 +829,7 @@ __device__ __forceinline__ bool gn_team_exchange(const GnArgs& p, int u, int m, 
     return true;
 }
 
-template <int NT, int NPT>
+template <int NT, int NPT, bool LO = false>
 __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
     __shared__ float red[NT * 16];
     __shared__ float chs[NT * 2];
@@ -789,7 +850,9 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
     const floatx4* gp = reinterpret_cast<const floatx4*>(p.gamma + cb + (active ? c0 : 0) * 8);
     const floatx4* bp = reinterpret_cast<const floatx4*>(p.beta + cb + (active ? c0 : 0) * 8);
     const floatx4 ga = gp[0], gb = gp[1], ba = bp[0], bb = bp[1];
-    half8 v[NPT];
+    half8 v[NPT], w[LO ? NPT : 1];
+    GnLoCol lcol = {nullptr, 0.f};
+    if constexpr (LO) lcol = gn_lo_col(p, cb + (active ? c0 : 0) * 8, col);
     float s[8], q[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s[e] = 0.f; q[e] = 0.f; }
@@ -798,14 +861,22 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
         for (int k = 0; k < NPT; ++k) {
             const int r = r0 + rl + k * nrl;
             v[k] = ld8(col.p + (brow + (size_t)(r < r_end ? r : (r0 < p.HW ? r0 : 0))) * col.pitch);
+            if constexpr (LO) w[k] = ld8(lcol.p + (brow + (size_t)(r < r_end ? r : (r0 < p.HW ? r0 : 0))) * col.pitch);
         }
         float piv[8];                                            // see gn_pivot: the same value in every member of the unit
         gn_pivots8(p, b, cb + c0 * 8, cpg, piv);
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = r0 + rl + k * nrl < r_end;
+            if constexpr (LO) {
+                float xv[8];
+                gn_val8(v[k], w[k], lcol.m, xv);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
+            } else {
 #pragma unroll
             for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
+            }
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f);
@@ -835,10 +906,12 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const int r = r0 + rl + k * nrl;
+        float xv[8];
+        if constexpr (LO) gn_val8(v[k], w[k], lcol.m, xv);
         half8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float yv = (float)v[k][e] * sc[e] + sh[e];
+            float yv = (LO ? xv[e] : (float)v[k][e]) * sc[e] + sh[e];
             if (p.fuse_silu) yv = silu_f(yv);
             o[e] = (half_t)yv;
         }
@@ -948,26 +1021,38 @@ struct LnArgs {
     const float* fin_partial;   // bwd: dy is a deferred split-K GEMM (slabs [fin_splits][M][C] + its epilogue), see GnArgs
     int fin_splits;
     clora_epilogue_t fin_epi;
+    const half_t* x_lo;   // fwd kernels instantiated with LO (clora_layernorm_fwd_f16_lo): the rounding remainder of x, [M, C]; appended, see GnArgs
 };
 
-template <bool BWD>
+// LO (forward only): the row that is normalised is float(x) + float(x_lo); the sum is formed again at each of its three uses (the
+// same fp32 value every time) instead of holding the row as floats.
+template <bool LO>
+__device__ __forceinline__ float ln_val(const half8& hi, const half8& lo, int e) {
+    if constexpr (LO) return (float)hi[e] + (float)lo[e];
+    else return (float)hi[e];
+}
+
+template <bool BWD, bool LO = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
+    static_assert(!(BWD && LO), "the backward recomputes from x");
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + w;
     const bool rok = row < p.M;
     const int CH = p.C / 8;
     const size_t off = (size_t)(rok ? row : 0) * p.C;
-    half8 xv[kLnCols], gv[kLnCols];
+    half8 xv[kLnCols], gv[kLnCols], lv[LO ? kLnCols : 1];
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < kLnCols; ++j) {
         const int cc = l + 64 * j;
         xv[j] = zero8(); gv[j] = zero8();
+        if constexpr (LO) lv[j] = zero8();
         if (cc < CH) {
             xv[j] = ld8(p.x + off + cc * 8);
             if (BWD) gv[j] = ld8(p.dy + off + cc * 8);
+            if constexpr (LO) lv[j] = ld8(p.x_lo + off + cc * 8);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) s += (float)xv[j][e];
+            for (int e = 0; e < 8; ++e) s += ln_val<LO>(xv[j], lv[LO ? j : 0], e);
         }
     }
     const float mean = wave_sum(s) / (float)p.C;
@@ -976,7 +1061,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
     for (int j = 0; j < kLnCols; ++j)
         if (l + 64 * j < CH) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { const float d = (float)xv[j][e] - mean; q += d * d; }
+            for (int e = 0; e < 8; ++e) { const float d = ln_val<LO>(xv[j], lv[LO ? j : 0], e) - mean; q += d * d; }
         }
     const float rstd = rsqrtf(wave_sum(q) / (float)p.C + p.eps);
     if (!BWD) {
@@ -987,7 +1072,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
                 half8 o;
 #pragma unroll
                 for (int e = 0; e < 8; ++e)
-                    o[e] = (half_t)(((float)xv[j][e] - mean) * rstd * p.gamma[cc * 8 + e] + p.beta[cc * 8 + e]);
+                    o[e] = (half_t)((ln_val<LO>(xv[j], lv[LO ? j : 0], e) - mean) * rstd * p.gamma[cc * 8 + e] + p.beta[cc * 8 + e]);
                 st8(p.y + off + cc * 8, o);
             }
         }
@@ -1033,13 +1118,14 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
 // 42 MB).  Here a wave issues the loads of ROWS rows (and gamma / beta, once) before the first reduction; per row the
 // arithmetic and its order are exactly those of layernorm_kernel, so the results are bit-identical.
 //   NC = 16-byte chunks per lane (C <= 512: 1, <= 1024: 2, <= 1536: 3)
-template <bool BWD, int NC, int ROWS, bool DEF = false>
+template <bool BWD, int NC, int ROWS, bool DEF = false, bool LO = false>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnArgs p) {
+    static_assert(!(BWD && LO), "the backward recomputes from x");
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + w) * ROWS;
     if (row0 >= p.M) return;                                     // wave-uniform
     const int CH = p.C / 8;
-    half8 xv[ROWS][NC], gv[ROWS][NC], rv[ROWS][NC];
+    half8 xv[ROWS][NC], gv[ROWS][NC], rv[ROWS][NC], lv[LO ? ROWS : 1][NC];
     float gam[NC][8], bet[NC][8];
     const bool has_res = BWD && p.dres != nullptr;               // kernel-uniform
     const half_t* res = has_res ? p.dres : p.x;                  // a valid address either way: the loads stay unconditional
@@ -1051,6 +1137,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnArgs p) {
         for (int j = 0; j < NC; ++j) {                           // branch-free: lanes past the row re-read chunk 0 (never used),
             const int cc = l + 64 * j, cl = cc < CH ? cc : 0;    // so every load of the wave is issued back to back
             xv[r][j] = ld8(p.x + off + cl * 8);
+            if constexpr (LO) lv[r][j] = ld8(p.x_lo + off + cl * 8);
             if (BWD) {
                 if constexpr (DEF) gv[r][j] = finish_chunk8(p.fin_partial, p.fin_splits, p.M, p.C, p.fin_epi, rok ? row0 + r : row0, cl * 8);
                 else gv[r][j] = ld8(p.dy + off + cl * 8);
@@ -1078,7 +1165,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnArgs p) {
         for (int j = 0; j < NC; ++j)
             if (l + 64 * j < CH) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) s += (float)xv[r][j][e];
+                for (int e = 0; e < 8; ++e) s += ln_val<LO>(xv[r][j], lv[LO ? r : 0][j], e);
             }
         mean[r] = wave_sum(s) / (float)p.C;
     }
@@ -1089,7 +1176,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnArgs p) {
         for (int j = 0; j < NC; ++j)
             if (l + 64 * j < CH) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) { const float d = (float)xv[r][j][e] - mean[r]; q += d * d; }
+                for (int e = 0; e < 8; ++e) { const float d = ln_val<LO>(xv[r][j], lv[LO ? r : 0][j], e) - mean[r]; q += d * d; }
             }
         rstd[r] = rsqrtf(wave_sum(q) / (float)p.C + p.eps);
     }
@@ -1104,7 +1191,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(LnArgs p) {
                 if (cc < CH && rok) {
                     half8 o;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (half_t)(((float)xv[r][j][e] - mean[r]) * rstd[r] * gam[j][e] + bet[j][e]);
+                    for (int e = 0; e < 8; ++e) o[e] = (half_t)((ln_val<LO>(xv[r][j], lv[LO ? r : 0][j], e) - mean[r]) * rstd[r] * gam[j][e] + bet[j][e]);
                     st8(p.y + off + cc * 8, o);
                 }
             }
@@ -1149,22 +1236,22 @@ bool ln_rows_plan(const LnArgs& a, bool bwd) {
     return clora_ln_rows() && a.C / 8 <= 192 && al16;
 }
 
-template <bool BWD, bool DEF = false>
+template <bool BWD, bool DEF = false, bool LO = false>
 void launch_layernorm(const LnArgs& a, hipStream_t s) {
     const int CH = a.C / 8;
     if (ln_rows_plan(a, BWD)) {
         if (a.M >= 2048) {                                       // enough rows to keep the chip full with fewer, fatter waves
-            if (CH <= 64) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 1, 4, DEF>), dim3(clora_cdiv(a.M, 16)), dim3(256), 0, s, a);
-            else if (CH <= 128) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 2, 2, DEF>), dim3(clora_cdiv(a.M, 8)), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 3, 2, DEF>), dim3(clora_cdiv(a.M, 8)), dim3(256), 0, s, a);
+            if (CH <= 64) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 1, 4, DEF, LO>), dim3(clora_cdiv(a.M, 16)), dim3(256), 0, s, a);
+            else if (CH <= 128) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 2, 2, DEF, LO>), dim3(clora_cdiv(a.M, 8)), dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 3, 2, DEF, LO>), dim3(clora_cdiv(a.M, 8)), dim3(256), 0, s, a);
         } else {                                                 // few rows (16x16 level, text tokens): one row per wave, but its 1-3 chunk
-            if (CH <= 64) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 1, 1, DEF>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);        // loads (and dy, dres, gamma)
-            else if (CH <= 128) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 2, 1, DEF>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);  // issued together instead of
-            else hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 3, 1, DEF>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);                 // one block per chunk
+            if (CH <= 64) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 1, 1, DEF, LO>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);        // loads (and dy, dres, gamma)
+            else if (CH <= 128) hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 2, 1, DEF, LO>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);  // issued together instead of
+            else hipLaunchKernelGGL((layernorm_rows_kernel<BWD, 3, 1, DEF, LO>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);                 // one block per chunk
         }
         return;
     }
-    hipLaunchKernelGGL((layernorm_kernel<BWD>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((layernorm_kernel<BWD, LO>), dim3(clora_cdiv(a.M, 4)), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------ row softmax
@@ -1330,7 +1417,7 @@ int gn_team_plan(GnArgs& a, bool bwd, bool params, void* state, size_t state_byt
     return pick_npt <= 4 ? 4 : (pick_npt <= 8 ? 8 : 16);
 }
 
-template <bool BWD>
+template <bool BWD, bool LO = false>
 void gn_team_launch(GnArgs& a, int npt, hipStream_t s) {
     const dim3 grid(kTeamBlocks), block(kTeamNT);
     for (int pass = CLORA_SEQUENTIAL_BLOCKS ? 0 : 1; pass < 2; ++pass) {
@@ -1339,9 +1426,9 @@ void gn_team_launch(GnArgs& a, int npt, hipStream_t s) {
             if (npt == 4) hipLaunchKernelGGL((gn_bwd_team_kernel<kTeamNT, 4>), grid, block, 0, s, a);
             else hipLaunchKernelGGL((gn_bwd_team_kernel<kTeamNT, 8>), grid, block, 0, s, a);
         } else {
-            if (npt == 4) hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 4>), grid, block, 0, s, a);
-            else if (npt == 8) hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 8>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 16>), grid, block, 0, s, a);
+            if (npt == 4) hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 4, LO>), grid, block, 0, s, a);
+            else if (npt == 8) hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 8, LO>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((gn_fwd_team_kernel<kTeamNT, 16, LO>), grid, block, 0, s, a);
         }
     }
 }
@@ -1374,8 +1461,11 @@ namespace {
 int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_deferred_t* src, clora_half* xcopy,
                 clora_half* y, const float* gamma, const float* beta, float* stats, int B, int HW, int C,
                 int G, float eps, int fuse_silu, void* team_state, size_t team_state_bytes, void* workspace, size_t workspace_bytes,
-                void* stream) {
+                void* stream, const clora_half* x_lo = nullptr, const clora_half* x2_lo = nullptr) {
     if (!y || !gamma || !beta || !stats) return CLORA_ERR_ARG;
+    if (!x2) x2_lo = nullptr;                                    // the remainder of a half that is not there
+    const bool lo = x_lo || x2_lo;                               // the plans are those of the plain call; only the instantiations differ
+    if (lo && src && src->splits > 0) return CLORA_ERR_ARG;      // a launch that writes a remainder is never deferred
     if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || G > 64 || (C % G) || (C & 7) || C > 4096) return CLORA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const bool deferred = src && src->splits > 0;
@@ -1388,6 +1478,7 @@ int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_d
     a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.stats = stats;
     a.B = B; a.HW = HW; a.C = C; a.G = G; a.eps = eps; a.fuse_silu = fuse_silu;
     a.x2 = (const half_t*)x2; a.Ca = x2 ? Ca : C; a.xcopy = (half_t*)xcopy;
+    a.x_lo = (const half_t*)x_lo; a.x2_lo = (const half_t*)x2_lo;
     const GnResident res = gn_resident_plan(a, false, false);
     // Folding pays only where a thread owns few rows (npt <= 4: the 8x8 / 16x16 maps): the one-launch kernels run 32-128 blocks and a
     // thread's rows are folded one after the other -- measured on MI355X (profiles/r06_deferred_ab.txt): 9.6 us against 6.6 + 6.0 for
@@ -1405,12 +1496,21 @@ int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_d
         GnArgs ta = a;
         const int npt = gn_team_plan(ta, false, false, team_state, team_state_bytes);
         if (npt) {
-            gn_team_launch<false>(ta, npt, s);
+            if (lo) gn_team_launch<false, true>(ta, npt, s);
+            else gn_team_launch<false>(ta, npt, s);
             return clora_check_launch();
         }
     }
     if (res.nt) {
         const dim3 rgrid(1, a.nslab, B);
+        if (lo) {
+            if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4, false, true>), rgrid, dim3(256), 0, s, a);
+            else if (res.nt == 256 && res.npt == 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 8, false, true>), rgrid, dim3(256), 0, s, a);
+            else if (res.nt == 256) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 16, false, true>), rgrid, dim3(256), 0, s, a);
+            else if (res.npt <= 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 8, false, true>), rgrid, dim3(512), 0, s, a);
+            else hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 16, false, true>), rgrid, dim3(512), 0, s, a);
+            return clora_check_launch();
+        }
         if (deferred_here) {
             a.fin_partial = src->partial; a.fin_splits = src->splits; a.fin_epi = src->epi; a.xcopy = (half_t*)src->C;
             if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4, true>), rgrid, dim3(256), 0, s, a);
@@ -1430,6 +1530,19 @@ int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_d
     int rc = gn_plan(a, workspace, workspace_bytes, false, false);
     if (rc != CLORA_OK) return rc;
     const dim3 grid(a.nchunk, a.nslab, B);
+    if (lo) {                                                    // the same three forms as below
+        if (a.CS / 8 > 256) {
+            hipLaunchKernelGGL((gn_fwd_partial_kernel<2, 1, true>), grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((gn_fwd_apply2_kernel<2, 1, true>), grid, dim3(256), 0, s, a);
+        } else if (clora_option(CLORA_OPT_GN_UNROLL)) {
+            hipLaunchKernelGGL((gn_fwd_partial_kernel<1, 2, true>), grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((gn_fwd_apply2_kernel<1, 2, true>), grid, dim3(256), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((gn_fwd_partial_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((gn_fwd_apply2_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
+        }
+        return clora_check_launch();
+    }
     if (a.CS / 8 > 256) {                                        // slabs wider than 2048 channels: two column chunks per thread
         hipLaunchKernelGGL(gn_fwd_partial_kernel<2>, grid, dim3(256), 0, s, a);
         hipLaunchKernelGGL(gn_fwd_apply2_kernel<2>, grid, dim3(256), 0, s, a);
@@ -1460,6 +1573,14 @@ extern "C" int clora_groupnorm_fwd_f16_team(const clora_half* x, const clora_hal
                                             size_t workspace_bytes, void* stream) {
     return gn_fwd_impl(x, x2, Ca, src, xcopy, y, gamma, beta, stats, B, HW, C, G, eps, fuse_silu, team_state, team_state_bytes, workspace,
                        workspace_bytes, stream);
+}
+
+extern "C" int clora_groupnorm_fwd_f16_lo(const clora_half* x, const clora_half* x2, int Ca, const clora_deferred_t* src, clora_half* xcopy,
+                                          clora_half* y, const float* gamma, const float* beta, float* stats, int B, int HW, int C,
+                                          int G, float eps, int fuse_silu, void* team_state, size_t team_state_bytes, void* workspace,
+                                          size_t workspace_bytes, const clora_half* x_lo, const clora_half* x2_lo, void* stream) {
+    return gn_fwd_impl(x, x2, Ca, src, xcopy, y, gamma, beta, stats, B, HW, C, G, eps, fuse_silu, team_state, team_state_bytes, workspace,
+                       workspace_bytes, stream, x_lo, x2_lo);
 }
 
 extern "C" int clora_groupnorm_fwd_f16(const clora_half* x, clora_half* y, const float* gamma, const float* beta,
@@ -1565,6 +1686,16 @@ extern "C" int clora_layernorm_fwd_f16(const clora_half* x, clora_half* y, const
     LnArgs a = LnArgs();
     a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.M = M; a.C = C; a.eps = eps;
     launch_layernorm<false>(a, (hipStream_t)stream);
+    return clora_check_launch();
+}
+
+extern "C" int clora_layernorm_fwd_f16_lo(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M,
+                                          int C, float eps, const clora_half* x_lo, void* stream) {
+    if (!x_lo) return clora_layernorm_fwd_f16(x, y, gamma, beta, M, C, eps, stream);
+    if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || (C & 7) || C / 8 > 64 * kLnCols) return CLORA_ERR_ARG;
+    LnArgs a = LnArgs();
+    a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.M = M; a.C = C; a.eps = eps; a.x_lo = (const half_t*)x_lo;
+    launch_layernorm<false, false, true>(a, (hipStream_t)stream);
     return clora_check_launch();
 }
 

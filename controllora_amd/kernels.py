@@ -213,14 +213,17 @@ def gemm(A: torch.Tensor, Bw: torch.Tensor, M: int, N: int, K: int, *, lda: Opti
     # compensated residual trunk (clora_epilogue_t.residual_lo / c_lo): inside a TrunkLo window every launch that
     # adds a residual -- the x + f(x) sums of the UNet -- and every launch flagged `trunk` (proj_in, the shortcut convs: where a trunk
     # segment starts) also writes the rounding remainder of its output; the launch whose residual is that output picks it up
-    c_lo = None
+    c_lo = trunk_hit = None
     want_lo_out = not _TRUNK_NO_OUT[0]
     if _TRUNK_LO_ON[0] and not geglu and C_ is not None and C_.dim() == 2 and (residual is not None or (trunk and want_lo_out)):
         if residual is not None:
-            hit = _TRUNK_LO.pop(residual.data_ptr(), None)
+            # (norms mode: a remainder lives until its last reader -- a down-path skip tensor is read again by the fork_cat norm of the up
+            # path --, so nothing is popped before the window closes)
+            hit = _TRUNK_LO.get(residual.data_ptr()) if _TRUNK_NORMS[0] else _TRUNK_LO.pop(residual.data_ptr(), None)
             if hit is not None and hit[0].numel() == residual.numel() and (residual.stride(0) if residual.dim() == 2 else N) == e.ldr:
                 e.residual_lo = ptr(hit[1], f16)
                 _trunk_keep[:] = [hit]                       # alive across this launch call (afterwards the allocator's stream order protects it)
+                trunk_hit = hit
         if want_lo_out:
             c_lo = torch.empty_strided(C_.shape, C_.stride(), dtype=f16, device=A.device)
             e.c_lo = ptr(c_lo)
@@ -251,7 +254,10 @@ def gemm(A: torch.Tensor, Bw: torch.Tensor, M: int, N: int, K: int, *, lda: Opti
     ws = workspace(GEMM_WS_BYTES if split_k == 0 else max(split_k, 1) * M * N * 4, A.device) if split_k != 1 else None
     # ln (a LayerNormSlot): where one tile spans the output row (N = 320 on the 8-wave 320-column tiles) the launch also writes
     # LayerNorm(C) -- the norm that follows an attention out-projection / proj_in in every BasicTransformerBlock -- into ln.out
-    if ln is not None and ln.out is None and FUSE_LN and not geglu and conv is None and C_ is not None and C_.is_contiguous():
+    # (norms mode: the fused norm would read the rounded C of a launch that also writes its remainder -- the slot is not offered, the
+    # caller's norm runs as its own launch on C + c_lo; include/clora.h clora_layernorm_fwd_f16_lo)
+    if (ln is not None and ln.out is None and FUSE_LN and not geglu and conv is None and C_ is not None and C_.is_contiguous()
+            and not (_TRUNK_NORMS[0] and c_lo is not None)):
         tc = tile_cfg
         if lora_dpack is not None and tc not in (51, 52, 54, 55) and e.lora_seg % 320 == 0:
             tc = 54 if M >= 32768 else 55                    # what the library would pick (clora_gemm_f16_ex): made explicit
@@ -272,7 +278,8 @@ def gemm(A: torch.Tensor, Bw: torch.Tensor, M: int, N: int, K: int, *, lda: Opti
           flops=2.0 * M * N * K, nbytes=2.0 * (A.numel() + N * K + M * N),
           tag=f"{M}x{N}x{K}{'conv' if conv is not None else ''}")
     if d is not None and d.splits > 1:
-        _PENDING[C_.data_ptr()] = (d, (C_, bias, rowadd, residual, lora_t, lora_u, ws))     # operands stay alive until it is consumed
+        # operands stay alive until it is consumed -- the (hi, lo) pair of the residual's remainder among them (the finish reads it)
+        _PENDING[C_.data_ptr()] = (d, (C_, bias, rowadd, residual, lora_t, lora_u, ws, trunk_hit))
         task = _graph_task_id()
         if task >= 0 and _pending_task[0] != task:       # inside a backward pass: whatever nobody consumed is finished when the pass ends
             _pending_task[0] = task
@@ -288,28 +295,52 @@ def gemm(A: torch.Tensor, Bw: torch.Tensor, M: int, N: int, K: int, *, lda: Opti
 _TRUNK_LO = {}
 _trunk_keep = []
 _TRUNK_LO_ON = [False]
-TRUNK_LO_MODE = os.environ.get("CLORA_TRUNK_LO", "infer")      # "infer": forwards without autograd; "always"; "off"
+_TRUNK_NORMS = [False]
+# CLORA_TRUNK_LO: "infer" (default): forwards without autograd carry the compensated trunk; "always": training forwards too; "off";
+# "norms": as "infer", and every GroupNorm / LayerNorm forward whose input has a remainder normalises float(hi) + float(lo)
+# (clora_groupnorm_fwd_f16_lo / clora_layernorm_fwd_f16_lo) -- never under autograd: the norm backwards recompute from x.
+# "norms" against "infer" on one MI355X (tools/trunk_norms_ab.py, profiles/trunk_norms_ab.txt): DDIM-50 latents 1.370 -> 1.224e-3 from the
+# fp32 oracle, +2.7 % sampler time, +6.6 GiB peak memory at UNet batch 32.
+TRUNK_LO_MODE = os.environ.get("CLORA_TRUNK_LO", "infer")      # (any other value behaves as "off", as before)
 
 
 class TrunkLo:
     """`with TrunkLo(enabled):` around ONE UNet forward: residual sums continue from their un-rounded values (see gemm).  The
-    remainders live until the window closes (a captured hipGraph keeps the kernels, not these tensors)."""
+    remainders live until the window closes (a captured hipGraph keeps the kernels, not these tensors).
+    norms=True: the norms read the remainders too (trunk_lo_of); a remainder then stays registered until the window closes instead of
+    being handed over to the one residual add that reads it -- at UNet batch 32 that is every trunk sum of a forward alive at once."""
 
-    def __init__(self, enabled: bool):
+    def __init__(self, enabled: bool, norms: bool = False):
         self.enabled = bool(enabled)
+        self.norms = self.enabled and bool(norms)
 
     def __enter__(self):
-        self.prev = _TRUNK_LO_ON[0]
+        self.prev, self.prev_norms = _TRUNK_LO_ON[0], _TRUNK_NORMS[0]
         if self.enabled and not self.prev:
             _TRUNK_LO.clear(); _trunk_keep.clear()
         _TRUNK_LO_ON[0] = self.enabled or self.prev
+        _TRUNK_NORMS[0] = self.norms or self.prev_norms
         return self
 
     def __exit__(self, *exc):
-        _TRUNK_LO_ON[0] = self.prev
+        _TRUNK_LO_ON[0], _TRUNK_NORMS[0] = self.prev, self.prev_norms
         if not self.prev:
             _TRUNK_LO.clear(); _trunk_keep.clear()
         return False
+
+
+def trunk_lo_of(x: torch.Tensor, *also) -> Optional[torch.Tensor]:
+    """the rounding remainder registered for the trunk tensor `x` (any view of its whole storage) for a norm that reads hi + lo, or
+    None: outside a TrunkLo(True, norms=True) window, when nothing wrote one, or when `x` (or one of `also`: the other inputs of the
+    same norm) takes part in autograd -- the norm backwards recompute from x alone, so a forward of hi + lo would not match them.
+    The callers are autograd.Function forwards, where torch.is_grad_enabled() is always False: requires_grad of the inputs is what
+    tells (UNet.forward opens a norms window only without autograd, this guards a window opened by hand).  The entry stays registered."""
+    if not (_TRUNK_NORMS[0] and _TRUNK_LO) or torch.is_grad_enabled() or x.requires_grad or any(t.requires_grad for t in also):
+        return None
+    hit = _TRUNK_LO.get(x.data_ptr())
+    if hit is None or hit[0].numel() != x.numel() or not hit[0].is_contiguous() or not x.is_contiguous():
+        return None
+    return hit[1].view(x.shape)
 
 
 _TRUNK_NO_OUT = [False]
@@ -320,8 +351,9 @@ class TrunkNoOut:
     caller knows that no residual add reads this sum (a transformer's last FeedForward sum feeds proj_out as an operand; up-path block
     outputs go into a channel concatenation)."""
 
-    def __init__(self, cond: bool = True):
-        self.cond = bool(cond)
+    def __init__(self, cond: bool = True, norm_reads: bool = False):
+        # norm_reads: a norm is the next reader of the sum -- in norms mode (TrunkLo(True, norms=True)) it wants the remainder
+        self.cond = bool(cond) and not (norm_reads and _TRUNK_NORMS[0])
 
     def __enter__(self):
         self.prev = _TRUNK_NO_OUT[0]
@@ -334,7 +366,11 @@ class TrunkNoOut:
 
 
 def trunk_lo_wanted() -> bool:
-    return TRUNK_LO_MODE == "always" or (TRUNK_LO_MODE == "infer" and not torch.is_grad_enabled())
+    return TRUNK_LO_MODE == "always" or (TRUNK_LO_MODE in ("infer", "norms") and not torch.is_grad_enabled())
+
+
+def trunk_norms_wanted() -> bool:
+    return TRUNK_LO_MODE == "norms" and not torch.is_grad_enabled()
 
 
 PATCH_TILE_CFGS = (71, 72, 73, 74, 75, 76, 77, 78, 79)     # conv3x3_patch_kernel variants of clora_gemm_f16_ex (77, 78: 392-pixel patch, rows >= 128 wide; 79: 256x160)
@@ -523,10 +559,12 @@ def _gn_ws(B, HW, Cc, G, device, bwd, params):
     return workspace(n, device)
 
 
-def groupnorm_fwd(x, gamma, beta, G, eps, silu, x2=None):
+def groupnorm_fwd(x, gamma, beta, G, eps, silu, x2=None, x_lo=None, x2_lo=None):
     """x2: the input is the channel concatenation cat(x, x2) read in place -> (y, stats, xcat) with xcat the concatenated
     tensor (written once by the kernel for the shortcut / backward).  If x is the still-unfinished output of a deferred split-K
-    GEMM (take_pending) the kernel folds the slabs while it loads and stores the finished x."""
+    GEMM (take_pending) the kernel folds the slabs while it loads and stores the finished x.
+    x_lo / x2_lo: the rounding remainders of x / x2 (same shapes; either or both): the kernels normalise float(hi) + float(lo)
+    (clora_groupnorm_fwd_f16_lo); xcat stays the concatenation of x and x2.  Without a remainder: the call of before."""
     B, HW, Ca = x.shape
     Cc = Ca + (x2.shape[-1] if x2 is not None else 0)
     src, _keep = take_pending(x)
@@ -538,6 +576,15 @@ def groupnorm_fwd(x, gamma, beta, G, eps, silu, x2=None):
         src = None
     ws = _gn_ws(B, HW, Cc, G, x.device, False, False)
     team = gn_team_state(x.device)
+    if x_lo is not None or x2_lo is not None:
+        assert x_lo is None or (x_lo.shape == x.shape and x_lo.is_contiguous())
+        assert x2_lo is None or (x2 is not None and x2_lo.shape == x2.shape and x2_lo.is_contiguous())
+        assert x.is_contiguous() and (x2 is None or x2.is_contiguous())
+        _call("clora_groupnorm_fwd_f16_lo", ptr(x, f16), ptr(x2, f16) if x2 is not None else None, Ca if x2 is not None else 0,
+              C.byref(src) if src is not None else None, ptr(xcat) if xcat is not None else None, ptr(y), ptr(gamma, f32), ptr(beta, f32),
+              ptr(stats), B, HW, Cc, G, float(eps), int(silu), ptr(team), team.numel(), ptr(ws), ws.numel(),
+              ptr(x_lo, f16) if x_lo is not None else None, ptr(x2_lo, f16) if x2_lo is not None else None)
+        return (y, stats, xcat) if x2 is not None else (y, stats)
     _call("clora_groupnorm_fwd_f16_team", ptr(x, f16), ptr(x2, f16) if x2 is not None else None, Ca if x2 is not None else 0,
           C.byref(src) if src is not None else None, ptr(xcat) if xcat is not None else None, ptr(y), ptr(gamma, f32), ptr(beta, f32),
           ptr(stats), B, HW, Cc, G, float(eps), int(silu), ptr(team), team.numel(), ptr(ws), ws.numel())
@@ -576,9 +623,15 @@ def groupnorm_bwd(x, dy, gamma, beta, stats, G, silu, want_param_grads=False, gr
     return (dx, None, None) if grads_into is not None else (dx, dg, db)
 
 
-def layernorm_fwd(x, gamma, beta, eps):
+def layernorm_fwd(x, gamma, beta, eps, x_lo=None):
+    """x_lo: the rounding remainder of x (same shape): the rows normalised are float(x) + float(x_lo) (clora_layernorm_fwd_f16_lo)"""
     x2 = _c2(x)
     y = torch.empty_like(x)
+    if x_lo is not None:
+        assert x_lo.shape == x.shape and x_lo.is_contiguous()
+        _call("clora_layernorm_fwd_f16_lo", ptr(x2, f16), ptr(y), ptr(gamma, f32), ptr(beta, f32), x2.shape[0], x2.shape[1], float(eps),
+              ptr(x_lo, f16))
+        return y
     _call("clora_layernorm_fwd_f16", ptr(x2, f16), ptr(y), ptr(gamma, f32), ptr(beta, f32), x2.shape[0], x2.shape[1], float(eps))
     return y
 

@@ -185,7 +185,9 @@ class _GroupNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, G, eps, silu, fork):
-        y, stats = K.groupnorm_fwd(x, gamma, beta, G, eps, silu)
+        # K.trunk_lo_of: in norms mode (CLORA_TRUNK_LO=norms, forwards without autograd) a trunk tensor's norm reads hi + lo -- a resnet's
+        # norm1, a transformer's norm, conv_norm_out; a conv output (ResnetBlock2D.norm2) has no remainder and runs as before
+        y, stats = K.groupnorm_fwd(x, gamma, beta, G, eps, silu, x_lo=K.trunk_lo_of(x))
         ctx.save_for_backward(x, gamma, beta, stats)
         ctx.cfg = (G, silu)
         ctx.affine = (gamma, beta)              # the Parameter objects (leaf tensors) when the norm is trainable
@@ -218,7 +220,8 @@ class _GroupNormCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, a, b, gamma, beta, G, eps, silu):
-        y, stats, xcat = K.groupnorm_fwd(a, gamma, beta, G, eps, silu, x2=b)
+        # norms mode: the remainders of both halves where they exist (the skip half's was written on the down path)
+        y, stats, xcat = K.groupnorm_fwd(a, gamma, beta, G, eps, silu, x2=b, x_lo=K.trunk_lo_of(a, b), x2_lo=K.trunk_lo_of(b, a))
         ctx.save_for_backward(xcat, gamma, beta, stats)
         ctx.cfg = (G, silu, a.shape[-1])
         return y, xcat
@@ -252,7 +255,7 @@ class _LayerNormFn(torch.autograd.Function):
         # backward is this function's as always
         ctx.save_for_backward(x, gamma)
         ctx.eps = eps
-        y = pre.view_as(x) if pre is not None else K.layernorm_fwd(x, gamma, beta, eps)
+        y = pre.view_as(x) if pre is not None else K.layernorm_fwd(x, gamma, beta, eps, x_lo=K.trunk_lo_of(x))
         return (y, x) if fork else y
 
     @staticmethod

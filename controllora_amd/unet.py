@@ -282,7 +282,8 @@ class Transformer2DModel(nn.Module):
 
     def forward(self, x, ehs, kw, out_to_norm=False, trunk_out=True):
         """out_to_norm: the caller feeds the result straight to a GroupNorm (see ops._FrozenLinearFn defer_out); trunk_out = False: no
-        residual add will read the result (it goes into a channel concatenation / the output norm): kernels.TrunkNoOut"""
+        residual add will read the result (it goes into a channel concatenation / the output norm): kernels.TrunkNoOut -- unless the
+        norms read the remainders too (CLORA_TRUNK_LO=norms) and a norm is the next reader (out_to_norm)"""
         B, N, C_ = x.shape
         grad = torch.is_grad_enabled() and x.requires_grad
         n, xr = self.norm.fork(x, False) if grad else (self.norm(x, False), x)
@@ -290,7 +291,7 @@ class Transformer2DModel(nn.Module):
         h = self.proj_in(n.reshape(B * N, C_), defer_dx=grad, ln=s1, trunk=True).reshape(B, N, -1)
         for i, blk in enumerate(self.transformer_blocks):
             h = blk(h, ehs, kw, pre_ln1=s1.out if i == 0 else None, last=i == len(self.transformer_blocks) - 1)
-        with K.TrunkNoOut(not trunk_out):
+        with K.TrunkNoOut(not trunk_out, norm_reads=out_to_norm):
             return self.proj_out(h.reshape(B * N, -1), xr.reshape(B * N, C_), defer_out=out_to_norm).reshape(B, N, C_)
 
 
@@ -326,7 +327,9 @@ class ResnetBlock2D(nn.Module):
         h = self.norm2(h.reshape(B, N, Cout), True).reshape(B * N, Cout)
         x2 = xr.reshape(B * N, Cin)
         sc = self.conv_shortcut(x2, trunk=True) if self.conv_shortcut is not None else x2
-        with K.TrunkNoOut(not trunk_out):              # (trunk_out = False: the result goes into a channel concatenation, see Transformer2DModel)
+        # (trunk_out = False: the result goes into a channel concatenation, see Transformer2DModel; norms mode: the norm that reads
+        # it there wants its remainder)
+        with K.TrunkNoOut(not trunk_out, norm_reads=out_to_norm):
             return self.conv2(h, B, H, W, residual=sc, defer_out=out_to_norm, defer_dx=grad).reshape(B, N, Cout)
 
 
@@ -520,8 +523,9 @@ class UNet2DConditionModel(nn.Module):
         ehs = encoder_hidden_states.to(f16).contiguous()
         from . import models as _models                  # (models imports this module: resolved at call time)
         # K.TrunkLo: every residual sum of this forward continues from the un-rounded previous sum (compensated trunk, kernels.gemm;
-        # by default for forwards without autograd -- the samplers --, CLORA_TRUNK_LO = always / off for A/B)
-        with _models.grouped_text_kv(self, ehs, kw), K.TrunkLo(K.trunk_lo_wanted()):     # training: the text K|V projections of all sites, one launch per width
+        # by default for forwards without autograd -- the samplers --, CLORA_TRUNK_LO = always / off for A/B; norms: the GroupNorm /
+        # LayerNorm forwards of trunk tensors read hi + lo as well)
+        with _models.grouped_text_kv(self, ehs, kw), K.TrunkLo(K.trunk_lo_wanted(), norms=K.trunk_norms_wanted()):     # training: the text K|V projections of all sites, one launch per width
             return self._forward_blocks(sample, temb_act, tp, ehs, kw, return_dict)
 
     def _forward_blocks(self, sample, temb_act, tp, ehs, kw, return_dict):

@@ -387,6 +387,28 @@ int clora_groupnorm_bwd_f16_team(const clora_half* x, const clora_half* dy, cons
                                  float* dgamma, float* dbeta, int B, int HW, int C, int G, int fuse_silu, int accumulate_params,
                                  void* team_state, size_t team_state_bytes, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Norm forwards that read the COMPENSATED TRUNK (new exports, ABI 4 unchanged; clora_epilogue_t.c_lo).  x_lo (layout and row pitch of x)
+ * and x2_lo (those of x2) are the rounding remainders fp16(v - fp16(v)) that the launch which wrote x / x2 stored next to it; either may
+ * be NULL independently.  Every element is loaded as v = float(hi) + float(lo), once, and the statistics, the pivot subtraction and the
+ * output all use v; the pivot P itself stays a sample of x, and xcopy receives x / x2 only (it feeds an MFMA operand).  With both
+ * remainders NULL the call IS clora_groupnorm_fwd_f16_team, bit for bit, and an all-zero remainder gives the same bits; the plan
+ * (team, one block per slab, two launches) is the one `_team` picks for the shape, a NULL team state falls through as it does there.
+ * A deferred split-K source together with a remainder is CLORA_ERR_ARG: a launch that writes c_lo is never deferred.
+ * Error against fp64 of hi + lo: output and statistics within 8e-4 (the limits of the plain forms), 2.1e-4 measured, for group means
+ * up to 10 std, where the plain call on the same data is at 2.2e-3 (tests/trunk_norm_cases.py; the same figures on the host emulator and on an MI355X).  Forward only: the backwards recompute
+ * from x.
+ * LayerNorm fused into a GEMM (clora_epilogue_t.ln_out) normalises the ROUNDED values the epilogue stored to C and has no flag to do
+ * otherwise, so a caller that wants the norm of hi + lo does not offer ln_out to a launch that writes c_lo and runs
+ * clora_layernorm_fwd_f16_lo as a launch of its own: up to 15 more launches per SD-1.5 UNet forward (the level-0 norm1 / norm2 / norm3
+ * of the 5 transformer blocks at 320 channels).  A later ABI revision could hand the epilogue's un-rounded fp32 v to its fused
+ * LayerNorm for free and take those launches back. */
+int clora_groupnorm_fwd_f16_lo(const clora_half* x, const clora_half* x2, int Ca, const clora_deferred_t* src, clora_half* xcopy,
+                               clora_half* y, const float* gamma, const float* beta, float* stats, int B, int HW, int C, int G,
+                               float eps, int fuse_silu, void* team_state, size_t team_state_bytes, void* workspace,
+                               size_t workspace_bytes, const clora_half* x_lo, const clora_half* x2_lo, void* stream);
+int clora_layernorm_fwd_f16_lo(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M, int C,
+                               float eps, const clora_half* x_lo, void* stream);
+
 /* ---- row softmax  y[r,:] = softmax(scale * x[r,:])  (fp32 max/sum; cols % 8 == 0, cols <= 8192, scale > 0; in place
  * allowed).  Normalises the materialised scores of the VAE's single-head d=512 attention (upstream AutoencoderKL
  * AttentionBlock, used at reference train_text_to_image_control_lora.py:753 / apps/gradio_canny2image.py). */
