@@ -44,6 +44,15 @@ class Epilogue(C.Structure):
                 ("residual_lo", C.c_void_p), ("c_lo", C.c_void_p)]                                              # compensated trunk
 
 
+class GemmTile(C.Structure):
+    """mirror of clora_gemm_tile_t: one row of the library's tile table"""
+    _fields_ = [(n, C.c_int) for n in ("tile_cfg", "family", "bm", "bn", "wm", "wn", "nst", "bk", "flags", "caps")]
+
+
+TILE_RING, TILE_V1, TILE_EIGHT_PHASE, TILE_PATCH, TILE_PATCH_WIDE, TILE_STRIP = range(6)      # CLORA_TILE_*
+TILE_CAP_GEGLU, TILE_CAP_DPACK, TILE_CAP_LN, TILE_CAP_CONV = 1, 2, 4, 8                       # CLORA_TILE_CAP_*
+
+
 class Deferred(C.Structure):
     """mirror of clora_deferred_t: a split-K GEMM whose finish pass is left to the consumer of its output"""
     _fields_ = [("partial", C.c_void_p), ("splits", C.c_int), ("M", C.c_int), ("N", C.c_int), ("C", C.c_void_p), ("ldc", C.c_int),
@@ -144,6 +153,9 @@ _PROTOS = {
     "clora_layernorm_bwd_f16_ex": [_P, _P, C.POINTER(Deferred), _P, _P, _P, _I, _I, _F, _P],
     "clora_finish_deferred": [C.POINTER(Deferred), _P],
     "clora_gemm_ln_fusable": [_I, _I, _I, _I, _I],
+    "clora_gemm_tile_info": [_I, C.POINTER(GemmTile)],
+    "clora_gemm_tile_at": [_I, C.POINTER(GemmTile)],
+    "clora_gemm_fused_down_tile": [_I, _I, _I, C.POINTER(_I)],
     "clora_layernorm_fwd_f16": [_P, _P, _P, _P, _I, _I, _F, _P],
     "clora_softmax_rows_f16": [_P, _P, _I, _I, _I, _F, _P],
     "clora_layernorm_bwd_f16": [_P, _P, _P, _P, _P, _I, _I, _F, _P],
@@ -222,6 +234,23 @@ class Lib:
         self.cdll.clora_lora_wgrad_workspace_bytes.restype = C.c_size_t
         self.cdll.clora_rank_gram_ws_bytes.restype = C.c_size_t
         self._options_from_env()
+        self._derived = {}
+
+    def derived(self, key, make):
+        """make(self), computed once per loaded library: what the host code derives from the library's own answers (the tests swap
+        `_LIB` for emulator and mutant builds, so nothing of the kind lives in a module global)"""
+        if key not in self._derived:
+            self._derived[key] = make(self)
+        return self._derived[key]
+
+    def tiles(self) -> dict:
+        """tile_cfg -> GemmTile: the library's tile table (clora_gemm_tile_at)"""
+        def read(L):
+            rows, r = {}, GemmTile()
+            while L.cdll.clora_gemm_tile_at(len(rows), C.byref(r)) == OK:
+                rows[r.tile_cfg], r = r, GemmTile()
+            return rows
+        return self.derived("tiles", read)
 
     # The library reads no environment variable; A/B runs set its knobs (clora_set_option, the ABI's single piece of
     # process-global state) through these variables, forwarded here when the library is loaded.

@@ -2083,6 +2083,104 @@ void pick_tile_order(GemmArgs& a, int BM, int BN, int splits, bool patch) {
     }
 }
 
+// ---- the tile table: ONE row per tile_cfg of clora_gemm_f16_ex (clora_gemm_tile_t, include/clora.h) ------------------------
+// The two launch switches, the capability checks, the replacement rules and the exports clora_gemm_tile_info / _tile_at /
+// _fused_down_tile all read these rows; Python and the tests read them through the exports.  Adding a tile = adding a row.
+//   FAMILY(tile_cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps)        FLAGS 1: fragment reads before the ring refill, 2: round-1 swizzle key
+// The rows stand in the order in which the kernels joined the library: it fixes the order of the kernels in the code object.
+constexpr int kG = CLORA_TILE_CAP_GEGLU, kD = CLORA_TILE_CAP_DPACK, kL = CLORA_TILE_CAP_LN, kC = CLORA_TILE_CAP_CONV;
+#define CLORA_GEMM_TILES(RING, V1, EIGHT, PATCH, WPATCH, STRIP)                                                                      \
+    PATCH(71, 256, 128, 4, 2, 3, 64, 0, 0)          /* conv3x3_patch_kernel: 3x3 stride-1 pad-1 convs, their dgrads, conv(nearest-2x(x)); the   */ \
+    PATCH(72, 128, 128, 2, 4, 3, 64, 0, 0)          /* input patch of BM pixels is staged once per 64-channel slab.  8 waves of 64x64 / 64x32 / */ \
+    PATCH(73, 128, 128, 4, 2, 3, 64, 0, 0)          /* 32x64 / 32x64 / 32x32; a shape the tile cannot take (patch_eligible) runs on 21          */ \
+    PATCH(74, 256, 64, 8, 1, 4, 64, 0, 0)                                                                                            \
+    PATCH(75, 128, 64, 4, 2, 4, 64, 0, 0)                                                                                            \
+    WPATCH(77, 128, 128, 2, 4, 3, 64, 0, 0)         /* the 392-pixel patch: one 128-pixel image row or row segment per tile (W = 128, 256, 512) */ \
+    WPATCH(78, 128, 64, 4, 2, 4, 64, 0, 0)                                                                                           \
+    PATCH(79, 256, 160, 4, 2, 3, 64, 0, 0)          /* 64x80 wave tiles, exactly 160 KB of LDS: batch >= 8 / inference at N = 320 .. 1280        */ \
+    PATCH(76, 128, 160, 4, 2, 3, 64, 0, 0)          /* 32x80 wave tiles: the UNet widths 320 / 640 / 960 / 1280 are multiples of 160, not of 128 */ \
+    RING(1, 128, 128, 2, 2, 3, 32, 0, kG | kC)      /* gemm_dma_kernel, BK 32, 3-stage LDS-DMA ring: what the latency model chooses among        */ \
+    RING(2, 128, 64, 4, 1, 3, 32, 0, kC)                                                                                             \
+    RING(3, 64, 64, 2, 2, 3, 32, 0, kC)                                                                                              \
+    RING(4, 128, 128, 2, 2, 5, 32, 0, kG | kC)      /* 1..3 with the deep ring                                                                  */ \
+    RING(5, 128, 64, 4, 1, 6, 32, 0, kC)                                                                                             \
+    RING(6, 64, 64, 2, 2, 8, 32, 0, kC)                                                                                              \
+    RING(7, 256, 128, 2, 2, 3, 32, 0, kG | kC)      /* wave tile 128x64                                                                         */ \
+    RING(8, 256, 128, 2, 2, 3, 32, 1, kG | kC)                                                                                       \
+    RING(21, 128, 128, 2, 2, 2, 64, 0, kG | kD | kC) /* BK 64: 128-byte LDS rows, whole-line DMA                                                 */ \
+    RING(22, 128, 64, 4, 1, 3, 64, 0, kD | kC)                                                                                       \
+    RING(23, 64, 64, 2, 2, 3, 64, 0, kD | kC)                                                                                        \
+    RING(26, 128, 64, 4, 1, 2, 64, 0, kD | kC)                                                                                       \
+    RING(31, 128, 128, 2, 2, 3, 32, 1, kG | kC)     /* 1..3 with the fragment reads before the ring refill                                      */ \
+    RING(32, 128, 64, 4, 1, 3, 32, 1, kC)                                                                                            \
+    RING(33, 64, 64, 2, 2, 3, 32, 1, kC)                                                                                             \
+    RING(9, 128, 128, 2, 2, 3, 32, 2, kG | kC)      /* 1 with the round-1 (2-way conflicted) swizzle key (A/B runs)                             */ \
+    RING(51, 128, 320, 4, 2, 2, 64, 0, kD | kL | kC) /* 8 waves, one block per CU, the whole of N = 320 per tile: A crosses L2 -> LDS once       */ \
+    RING(52, 64, 320, 2, 4, 3, 64, 0, kD | kL | kC) /* (wave tiles 32x160 / 32x80 / 32x128: the short-K projections)                            */ \
+    RING(53, 128, 256, 4, 2, 3, 64, 0, kG | kC)                                                                                      \
+    RING(57, 256, 320, 4, 2, 2, 64, 1, kC)          /* M >= 32768 (batch-32 inference): 142 flop per operand byte; wave tiles 64x160 / 64x128   */ \
+    RING(58, 256, 256, 4, 2, 2, 64, 1, kG | kC)                                                                                      \
+    EIGHT(59, 256, 256, 2, 4, 0, 64, 0, kG)         /* gemm_8p_kernel: 8 waves of 128x64, eight-phase ping-pong; plain rows only: a conv runs on 58 */ \
+    RING(54, 128, 320, 4, 2, 2, 64, 1, kD | kL | kC) /* 51..53 with the fragment reads before the ring refill                                    */ \
+    RING(55, 64, 320, 2, 4, 3, 64, 1, kD | kL | kC)                                                                                  \
+    RING(56, 128, 256, 4, 2, 3, 64, 1, kG | kC)                                                                                      \
+    RING(41, 128, 128, 2, 2, 2, 64, 1, kG | kD | kC) /* 21..23 with the fragment reads before the ring refill                                    */ \
+    RING(42, 128, 64, 4, 1, 3, 64, 1, kD | kC)                                                                                       \
+    RING(43, 64, 64, 2, 2, 3, 64, 1, kD | kC)                                                                                        \
+    V1(11, 128, 128, 2, 2, 3, 32, 0, kC)            /* 1..3 on gemm_kernel, the register-staged round-1 loop (A/B runs): no DMA, no GEGLU, no   */ \
+    V1(12, 128, 64, 4, 1, 3, 32, 0, kC)             /* tile order                                                                               */ \
+    V1(13, 64, 64, 2, 2, 3, 32, 0, kC)                                                                                               \
+    STRIP(61, 0, 0, 0, 0, 0, 0, 0, 0)               /* conv3x3_strip_kernel (strip_plan picks its shape); a launch it cannot take runs as tile_cfg 0 */
+#ifdef CLORA_DMA_PROBE
+// timing probes (results are garbage): the A and / or B tiles are fetched from the 16-byte zero page -- the same DMA
+// instruction stream with no L2 -> LDS operand traffic.  Built only by tools/dma_probe.sh.
+#define CLORA_GEMM_PROBE_TILES(RING)                                                                                    \
+    RING(91, 128, 128, 2, 2, 2, 64, 4, 0) RING(92, 128, 128, 2, 2, 2, 64, 8, 0) RING(93, 128, 128, 2, 2, 2, 64, 12, 0)  \
+    RING(94, 128, 64, 4, 1, 2, 64, 4, 0) RING(95, 128, 64, 4, 1, 2, 64, 8, 0) RING(96, 128, 64, 4, 1, 2, 64, 12, 0)
+#else
+#define CLORA_GEMM_PROBE_TILES(RING)
+#endif
+// (round 5, measured and removed: the 320-column tiles and the 128x160 / 128x128 patch tiles with FOUR waves = one wave per
+// SIMD, 512 registers, wave tiles 64x80 / 64x160 / 64x64 -- half the fragment reads per MFMA, but a lone wave per SIMD has
+// nobody to hide its LDS latency behind: 15..50 % SLOWER on every level-0 / level-1 shape, profiles/r05_onewave_ab.txt)
+// (round 5, measured and removed: conv3x3_patch_kernel with its two wave halves one barrier apart -- the ping-pong schedule of
+// gemm_8p_kernel, cfgs 84 / 86 / 89 at the time: parity green on hardware, 128x160 +0.5..1.5 % (noise level), the 256-row tiles
+// 25-60 % slower (spills); the lockstep tap loop is NOT what holds the patch convs at 43 % MFMA busy: profiles/r05_patch_pingpong_ab.txt)
+
+// what a gemm_dma_kernel tile can carry, from its template arguments (the epilogue's own conditions: BN % 128 == 0 for the GEGLU
+// forward's [64 a | 64 g] column groups, LN_TILE for ln_out); a row's capability bits must say the same
+constexpr bool tile_carries_dpack(int BM, int BN, int waves, int NST, int BK) {
+    return BK == 64 && ((waves == 8 && BN == 320 && BM <= 128) || (waves == 4 && BM * BN <= 128 * 128 && NST <= 3));
+}
+constexpr bool tile_takes_geglu(int BN) { return BN % 128 == 0; }
+constexpr bool tile_fuses_ln(int BM, int BN, int waves) { return BN == 320 && waves == 8 && (BM == 64 || BM == 128); }
+
+#define CLORA_ROW(FAM, cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) {cfg, FAM, BM, BN, WM, WN, NST, BK, FLAGS, caps},
+#define ROW_RING(...) CLORA_ROW(CLORA_TILE_RING, __VA_ARGS__)
+#define ROW_V1(...) CLORA_ROW(CLORA_TILE_V1, __VA_ARGS__)
+#define ROW_EIGHT(...) CLORA_ROW(CLORA_TILE_EIGHT_PHASE, __VA_ARGS__)
+#define ROW_PATCH(...) CLORA_ROW(CLORA_TILE_PATCH, __VA_ARGS__)
+#define ROW_WPATCH(...) CLORA_ROW(CLORA_TILE_PATCH_WIDE, __VA_ARGS__)
+#define ROW_STRIP(...) CLORA_ROW(CLORA_TILE_STRIP, __VA_ARGS__)
+constexpr clora_gemm_tile_t kTileRows[] = {CLORA_GEMM_TILES(ROW_RING, ROW_V1, ROW_EIGHT, ROW_PATCH, ROW_WPATCH, ROW_STRIP)
+                                           CLORA_GEMM_PROBE_TILES(ROW_RING)};
+constexpr int kNumTileRows = sizeof(kTileRows) / sizeof(kTileRows[0]);
+// an unknown tile_cfg: no capability, fails at the launch switch (BK 32 keeps the order of the error returns in front of it)
+constexpr clora_gemm_tile_t kNoTile = {-1, -1, 0, 0, 0, 0, 0, 32, 0, 0};
+
+#define CHECK_RING(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps)                                                                         \
+    static_assert((((caps) & kD) != 0) == tile_carries_dpack(BM, BN, (WM) * (WN), NST, BK), "tile " #cfg ": D bit");                 \
+    static_assert((((caps) & kG) != 0) == tile_takes_geglu(BN), "tile " #cfg ": G bit");                                             \
+    static_assert((((caps) & kL) != 0) == tile_fuses_ln(BM, BN, (WM) * (WN)), "tile " #cfg ": L bit");
+#define CHECK_OTHER(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) static_assert(((caps) & (kD | kL)) == 0, "tile " #cfg ": only the DMA ring carries D / L");
+CLORA_GEMM_TILES(CHECK_RING, CHECK_OTHER, CHECK_OTHER, CHECK_OTHER, CHECK_OTHER, CHECK_OTHER)
+
+const clora_gemm_tile_t& tile_row(int cfg) {
+    for (const clora_gemm_tile_t& r : kTileRows)
+        if (r.tile_cfg == cfg) return r;
+    return kNoTile;
+}
+
 template <int BM, int BN, int WM, int WN, int NST = 3, int BK = 32, int FLAGS = 0>
 int launch_gemm(GemmArgs& a, int splits, hipStream_t s, bool dma) {
     a.tiles_n = clora_cdiv(a.N, BN);
@@ -2091,7 +2189,7 @@ int launch_gemm(GemmArgs& a, int splits, hipStream_t s, bool dma) {
     if (!dma) { a.n_major = 0; a.xg_s = a.xg_m = a.xg_n = 0; }      // the v1 loop decodes blockIdx directly
     const dim3 grid(tiles_m * a.tiles_n, splits);
     if (dma && a.epi.lora_dpack) {
-        if constexpr (BK == 64 && ((WM * WN == 8 && BN == 320 && BM <= 128) || (WM * WN == 4 && BM * BN <= 128 * 128 && NST <= 3))) {
+        if constexpr (tile_carries_dpack(BM, BN, WM * WN, NST, BK)) {
             hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, WM, WN, NST, 0, BK, FLAGS, 8>), grid, dim3(WM * WN * 64), 0, s, a);
             return clora_check_launch();
         } else {
@@ -2137,6 +2235,11 @@ bool patch_eligible(const GemmArgs& a, int bm, int maxpp = 0) {
     return nimg * (rpi + 2) * (tw + 2) <= (maxpp > 0 ? maxpp : (bm == 256 ? 400 : 288));
 }
 
+bool is_patch_tile(const clora_gemm_tile_t& r) { return r.family == CLORA_TILE_PATCH || r.family == CLORA_TILE_PATCH_WIDE; }
+bool patch_eligible(const GemmArgs& a, const clora_gemm_tile_t& r) {
+    return patch_eligible(a, r.bm, r.family == CLORA_TILE_PATCH_WIDE ? kPatchWide : 0);
+}
+
 template <int BM, int BN, int WM, int WN, int NST, int MAXPP_ = 0>
 int launch_patch(GemmArgs& a, int splits, hipStream_t s) {
     a.tiles_n = clora_cdiv(a.N, BN);
@@ -2173,8 +2276,8 @@ int finish_or_defer(GemmArgs& a, int splits, clora_deferred_t* defer, hipStream_
 // Predictions are within ~15% of the sweep for the 15 UNet shapes; the model prefers split-K whenever
 // M*N alone gives fewer than ~3 blocks per CU (the 16x16 / 8x8 UNet levels are weight-streaming problems).
 namespace {
-struct TileCfg { int bm, bn, conc; double t_k; };
-const TileCfg kTiles[3] = {{128, 128, 3, 0.85e-6}, {128, 64, 4, 0.82e-6}, {64, 64, 6, 0.52e-6}};
+struct TileCfg { int cfg, conc; double t_k; };           // a tile the model chooses among: its row of the tile table + the model constants
+const TileCfg kTiles[3] = {{1, 3, 0.85e-6}, {2, 4, 0.82e-6}, {3, 6, 0.52e-6}};
 
 void plan_gemm(int M, int N, int K, int max_split, int& tile, int& splits) {
     const int ksteps = clora_cdiv(K, 32);
@@ -2182,7 +2285,8 @@ void plan_gemm(int M, int N, int K, int max_split, int& tile, int& splits) {
     tile = 0; splits = 1;
     for (int c = 0; c < 3; ++c) {
         const TileCfg& tc = kTiles[c];
-        const long tiles = (long)clora_cdiv(M, tc.bm) * clora_cdiv(N, tc.bn);
+        const clora_gemm_tile_t& r = tile_row(tc.cfg);
+        const long tiles = (long)clora_cdiv(M, r.bm) * clora_cdiv(N, r.bn);
         for (int s = 1; s <= max_split && s <= 16; ++s) {
             if (s > 1 && ksteps / s < 4) break;
             const int kps = clora_cdiv(ksteps, s);
@@ -2242,9 +2346,9 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
         split_k = 1;                                     // the fused activation lives in the main kernel's epilogue only
     }
     hipStream_t s = (hipStream_t)stream;
-    //   61 = conv3x3_strip_kernel (the hint encoder's large-map 3x3 convolutions and their dgrads: 32 / 64 input channels, <= 64 output
-    //        channels, kchunk 0, bias-only epilogue, C rows 8-byte aligned); anything it cannot take falls back to the library's own choice
-    if (tile_cfg == 61) {
+    // conv3x3_strip_kernel (the hint encoder's large-map 3x3 convolutions and their dgrads: 32 / 64 input channels, <= 64 output
+    // channels, kchunk 0, bias-only epilogue, C rows 8-byte aligned); anything it cannot take falls back to the library's own choice
+    if (tile_row(tile_cfg).family == CLORA_TILE_STRIP) {
         const int plan = (a.conv.enabled && split_k <= 1 && !defer && !a.epi.rowadd && !a.epi.residual && !a.epi.lora_t && !a.epi.geglu &&
                           !a.epi.ln_out && !a.epi.c_lo && C && (ldc & 3) == 0 && K == 9 * a.conv.Cin)
                              ? strip_plan(M, N, a.conv) : 0;
@@ -2268,48 +2372,30 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
         const int ksteps = clora_cdiv(K, 32);
         splits = split_k > ksteps ? ksteps : split_k;
     }
-    // tile_cfg: 0 = the latency model's choice among 1..3;
-    //   1..3  = 128x128 / 128x64 / 64x64, BK 32, 3-stage ring        4..6 = the same tiles with the deep ring (5 / 6 / 8 stages)
-    //   7, 8  = 256x128 (wave tile 128x64), BK 32, 3 stages; 8 reads its fragments before refilling the ring
-    //   11..13 = the register-staged v1 main loop (A/B comparisons)
-    //   9 = 1 with the round-1 (2-way conflicted) swizzle key, for A/B runs
-    //   21, 22, 23, 26 = BK 64 (128-byte LDS rows, whole-line DMA): 128x128 x2 stages, 128x64 x3, 64x64 x3, 128x64 x2
-    //   31..33 = 1..3 and 41..43 = 21..23 with fragment reads before the ring refill
-    //   51..53 = 8-wave blocks (one per CU), BK 64: 128x320 x2 stages, 64x320 x3, 128x256 x3 (wave tiles 32x160 / 32x80 / 32x128) for the
-    //            short-K projections -- with the whole of N = 320 in one tile A is fetched once instead of once per 64 / 128 columns;
-    //            54..56 = the same with fragment reads before the ring refill; 57, 58 = 256x320 / 256x256 x2 stages (wave tiles 64x160 /
-    //            64x128) for the M >= 32768 projections of the batch-32 inference forward
-    bool dma = true;
+    // tile_cfg: 0 = the latency model's choice (kTiles), else a row of the tile table
     if (a.epi.lora_dpack) {
-        // the adapter down-projection rides in this launch (clora_epilogue_t.lora_dpack): 8-wave 320-column tiles only
+        // the adapter down-projection rides in this launch (clora_epilogue_t.lora_dpack), on a tile with the D bit
         const clora_epilogue_t& e = a.epi;
         if (a.conv.enabled || !e.lora_t || e.lora_r != 4 || e.geglu || (e.lora_seg % 64) || (N % e.lora_seg) || (K & 63) || split_k > 1 ||
             (e.ldt & 3) || (e.lora_u_tr ? (e.ldu & 3) != 0 : e.ldu != 4) || N / e.lora_seg > 32 ||
             (e.lora_t_in && ((e.ldt_in & 3) || e.lora_t_in_rows < 0)))
             return CLORA_ERR_ARG;
-        // capable tiles: a tile must lie inside one column segment.  8-wave 320-column tiles (51 / 52 / 54 / 55), 64-column tiles
-        // (22 / 42 / 26: 128x64; 23 / 43: 64x64), 128x128 (21 / 41); anything else is replaced by the library's choice
-        const int bn = (tile_cfg == 51 || tile_cfg == 52 || tile_cfg == 54 || tile_cfg == 55) ? 320
-                     : (tile_cfg == 22 || tile_cfg == 42 || tile_cfg == 26 || tile_cfg == 23 || tile_cfg == 43) ? 64
-                     : (tile_cfg == 21 || tile_cfg == 41) ? 128 : 0;
-        if (bn == 0 || (e.lora_seg % bn)) {
-            if (e.lora_seg % 320 == 0) tile_cfg = M >= 32768 ? 54 : 55;
-            else tile_cfg = 43;
-        }
+        clora_gemm_fused_down_tile(M, e.lora_seg, tile_cfg, &tile_cfg);
         split_k = 1; splits = 1;
     }
-    if (tile_cfg >= 11 && tile_cfg <= 13) { dma = false; tile_cfg -= 10; }
-    int cfg = tile_cfg > 0 ? tile_cfg : tile + 1;
+    const clora_gemm_tile_t* row = &tile_row(tile_cfg > 0 ? tile_cfg : kTiles[tile].cfg);
+    const bool dma = row->family != CLORA_TILE_V1;
     // untuned shape (no table entry: tile_cfg == 0) that the patch-staged conv kernel can take: it beat every implicit-GEMM
     // variant on all 46 tuned signatures (profiles/r02_tune_patch.log), so it is the default there too -- 128-pixel tiles, 160
     // columns when the width allows, split over slabs until the grid covers the chip (split_k == 0) or as forced
     // (shapes only the WIDE patch can take -- rows of 128 pixels and more: the VAE's levels -- stay on the implicit GEMM: on MI355X
     // tile_cfg 77 ties it at 128 x 128 maps and loses 10-25 % at 256^2 / 512^2, profiles/r03_vae_conv_ab.txt: with 128 output columns
     // per tile the weight stream, which the patch does not reduce, dominates the operand traffic)
-    if (tile_cfg == 0 && dma && !a.epi.geglu && patch_eligible(a, 128)) {
-        cfg = (N % 160 == 0) ? 76 : 72;
+    const clora_gemm_tile_t& patch = tile_row((N % 160 == 0) ? 76 : 72);
+    if (tile_cfg == 0 && !a.epi.geglu && patch_eligible(a, patch)) {
+        row = &patch;
         if (split_k == 0) {
-            const long blocks = (long)clora_cdiv(M, 128) * clora_cdiv(N, cfg == 76 ? 160 : 128);
+            const long blocks = (long)clora_cdiv(M, patch.bm) * clora_cdiv(N, patch.bn);
             const int slabs = a.conv.Cin / 64;
             int want = (int)((256 + blocks - 1) / blocks);
             if (want > slabs) want = slabs;
@@ -2319,16 +2405,10 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
     }
     if (a.epi.geglu) {
         if (!dma) return CLORA_ERR_ARG;
-        const bool wide = cfg == 1 || cfg == 4 || cfg == 7 || cfg == 8 || cfg == 9 || cfg == 21 || cfg == 31 || cfg == 41 || cfg == 53 || cfg == 56 || cfg == 58 || cfg == 59;
-        if (a.epi.geglu == 1 && !wide) { if (tile_cfg > 0) return CLORA_ERR_ARG; cfg = 1; }
+        if (a.epi.geglu == 1 && !(row->caps & kG)) { if (tile_cfg > 0) return CLORA_ERR_ARG; row = &tile_row(1); }
     }
-    //   71..76 = conv3x3_patch_kernel (3x3 stride-1 pad-1 convs and their dgrads, input patch staged once per 64-channel slab):
-    //            256x128 (8 waves of 64x64), 128x128 (64x32), 128x128 (32x64), 256x64 (32x64), 128x64 (32x32), 128x160 (32x80: the
-    //            UNet widths 320 / 640 / 960 / 1280 are multiples of 160, not of 128); shapes it cannot take fall back to 21
-    //            77, 78 = 128x128 / 128x64 with the 392-pixel patch (one 128-pixel row or row segment per tile: W = 128, 256, 512)
-    //            79 = 256x160 (8 waves of 64x80; exactly 160 KB of LDS): batch >= 8 / inference shapes at N = 320 / 640 / 960 / 1280
-    if (cfg >= 71 && cfg <= 79) {
-        if (!dma || !patch_eligible(a, (cfg == 71 || cfg == 74 || cfg == 79) ? 256 : 128, (cfg == 77 || cfg == 78) ? kPatchWide : 0)) cfg = 21;
+    if (is_patch_tile(*row)) {
+        if (!patch_eligible(a, *row)) row = &tile_row(21);
         else {
             const int slabs = a.conv.Cin / 64;
             if (splits > slabs) splits = slabs;
@@ -2339,28 +2419,20 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
                 a.partial = (float*)workspace;
             }
             int rc;
-            switch (cfg) {
-                case 71: rc = launch_patch<256, 128, 4, 2, 3>(a, splits, s); break;
-                case 72: rc = launch_patch<128, 128, 2, 4, 3>(a, splits, s); break;
-                case 73: rc = launch_patch<128, 128, 4, 2, 3>(a, splits, s); break;
-                case 74: rc = launch_patch<256, 64, 8, 1, 4>(a, splits, s); break;
-                case 75: rc = launch_patch<128, 64, 4, 2, 4>(a, splits, s); break;
-                case 77: rc = launch_patch<128, 128, 2, 4, 3, kPatchWide>(a, splits, s); break;
-                case 78: rc = launch_patch<128, 64, 4, 2, 4, kPatchWide>(a, splits, s); break;
-                case 79: rc = launch_patch<256, 160, 4, 2, 3>(a, splits, s); break;
-                default: rc = launch_patch<128, 160, 4, 2, 3>(a, splits, s); break;
+            switch (row->tile_cfg) {
+#define CASE_PATCH(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) case cfg: rc = launch_patch<BM, BN, WM, WN, NST>(a, splits, s); break;
+#define CASE_WPATCH(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) case cfg: rc = launch_patch<BM, BN, WM, WN, NST, kPatchWide>(a, splits, s); break;
+#define CASE_NONE(...)
+                CLORA_GEMM_TILES(CASE_NONE, CASE_NONE, CASE_NONE, CASE_PATCH, CASE_WPATCH, CASE_NONE)
+                default: return CLORA_ERR_ARG;
             }
             if (rc != CLORA_OK) return rc;
             if (splits > 1) rc = finish_or_defer(a, splits, defer, s);
             return rc;
         }
     }
-    // (round 5, measured and removed: conv3x3_patch_kernel with its two wave halves one barrier apart -- the ping-pong schedule of
-    // gemm_8p_kernel, cfgs 84 / 86 / 89 at the time: parity green on hardware, 128x160 +0.5..1.5 % (noise level), the 256-row tiles
-    // 25-60 % slower (spills); the lockstep tap loop is NOT what holds the patch convs at 43 % MFMA busy: profiles/r05_patch_pingpong_ab.txt)
-    //   59 = gemm_8p_kernel: 256x256, 8 waves of 128x64, eight-phase ping-pong (plain GEMM rows only; convs fall back to 58)
-    if (cfg == 59 && (a.conv.enabled || !dma)) cfg = 58;
-    const int bk = ((cfg >= 21 && cfg <= 26) || (cfg >= 41 && cfg <= 43) || (cfg >= 51 && cfg <= 59) || (cfg >= 91 && cfg <= 96)) ? 64 : 32;
+    if (a.conv.enabled && row->family == CLORA_TILE_EIGHT_PHASE) row = &tile_row(58);       // the one main loop without the conv gather (no C bit)
+    const int bk = row->bk;
     a.k_per_split = clora_cdiv(clora_cdiv(K, bk), splits) * bk;
     splits = clora_cdiv(K, a.k_per_split);
     if (splits > 1) {
@@ -2368,48 +2440,12 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
         a.partial = (float*)workspace;
     }
     int rc;
-    switch (cfg) {
-        case 1: rc = launch_gemm<128, 128, 2, 2>(a, splits, s, dma); break;
-        case 2: rc = launch_gemm<128, 64, 4, 1>(a, splits, s, dma); break;
-        case 3: rc = launch_gemm<64, 64, 2, 2>(a, splits, s, dma); break;
-        case 4: rc = launch_gemm<128, 128, 2, 2, 5>(a, splits, s, true); break;
-        case 5: rc = launch_gemm<128, 64, 4, 1, 6>(a, splits, s, true); break;
-        case 6: rc = launch_gemm<64, 64, 2, 2, 8>(a, splits, s, true); break;
-        case 7: rc = launch_gemm<256, 128, 2, 2, 3, 32, 0>(a, splits, s, true); break;
-        case 8: rc = launch_gemm<256, 128, 2, 2, 3, 32, 1>(a, splits, s, true); break;
-        case 21: rc = launch_gemm<128, 128, 2, 2, 2, 64, 0>(a, splits, s, true); break;
-        case 22: rc = launch_gemm<128, 64, 4, 1, 3, 64, 0>(a, splits, s, true); break;
-        case 23: rc = launch_gemm<64, 64, 2, 2, 3, 64, 0>(a, splits, s, true); break;
-        case 26: rc = launch_gemm<128, 64, 4, 1, 2, 64, 0>(a, splits, s, true); break;
-        case 31: rc = launch_gemm<128, 128, 2, 2, 3, 32, 1>(a, splits, s, true); break;
-        case 32: rc = launch_gemm<128, 64, 4, 1, 3, 32, 1>(a, splits, s, true); break;
-        case 33: rc = launch_gemm<64, 64, 2, 2, 3, 32, 1>(a, splits, s, true); break;
-        case 9: rc = launch_gemm<128, 128, 2, 2, 3, 32, 2>(a, splits, s, true); break;     // round-1 swizzle key (A/B)
-        case 51: rc = launch_gemm<128, 320, 4, 2, 2, 64, 0>(a, splits, s, true); break;    // 8 waves, the whole of N = 320 per tile: A crosses L2 -> LDS once
-        case 52: rc = launch_gemm<64, 320, 2, 4, 3, 64, 0>(a, splits, s, true); break;
-        case 53: rc = launch_gemm<128, 256, 4, 2, 3, 64, 0>(a, splits, s, true); break;
-        case 57: rc = launch_gemm<256, 320, 4, 2, 2, 64, 1>(a, splits, s, true); break;    // M >= 32768 (batch-32 inference): 142 flop per operand byte
-        case 58: rc = launch_gemm<256, 256, 4, 2, 2, 64, 1>(a, splits, s, true); break;
-        case 59: rc = launch_gemm_8p(a, splits, s); break;
-        // (round 5, measured and removed: the 320-column tiles and the 128x160 / 128x128 patch tiles with FOUR waves = one wave per
-        // SIMD, 512 registers, wave tiles 64x80 / 64x160 / 64x64 -- half the fragment reads per MFMA, but a lone wave per SIMD has
-        // nobody to hide its LDS latency behind: 15..50 % SLOWER on every level-0 / level-1 shape, profiles/r05_onewave_ab.txt)
-        case 54: rc = launch_gemm<128, 320, 4, 2, 2, 64, 1>(a, splits, s, true); break;
-        case 55: rc = launch_gemm<64, 320, 2, 4, 3, 64, 1>(a, splits, s, true); break;
-        case 56: rc = launch_gemm<128, 256, 4, 2, 3, 64, 1>(a, splits, s, true); break;
-#ifdef CLORA_DMA_PROBE
-        // timing probes (results are garbage): the A and / or B tiles are fetched from the 16-byte zero page -- the same DMA
-        // instruction stream with no L2 -> LDS operand traffic.  Built only by tools/dma_probe.sh.
-        case 91: rc = launch_gemm<128, 128, 2, 2, 2, 64, 4>(a, splits, s, true); break;
-        case 92: rc = launch_gemm<128, 128, 2, 2, 2, 64, 8>(a, splits, s, true); break;
-        case 93: rc = launch_gemm<128, 128, 2, 2, 2, 64, 12>(a, splits, s, true); break;
-        case 94: rc = launch_gemm<128, 64, 4, 1, 2, 64, 4>(a, splits, s, true); break;
-        case 95: rc = launch_gemm<128, 64, 4, 1, 2, 64, 8>(a, splits, s, true); break;
-        case 96: rc = launch_gemm<128, 64, 4, 1, 2, 64, 12>(a, splits, s, true); break;
-#endif
-        case 41: rc = launch_gemm<128, 128, 2, 2, 2, 64, 1>(a, splits, s, true); break;
-        case 42: rc = launch_gemm<128, 64, 4, 1, 3, 64, 1>(a, splits, s, true); break;
-        case 43: rc = launch_gemm<64, 64, 2, 2, 3, 64, 1>(a, splits, s, true); break;
+    switch (row->tile_cfg) {
+#define CASE_RING(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) case cfg: rc = launch_gemm<BM, BN, WM, WN, NST, BK, FLAGS>(a, splits, s, true); break;
+#define CASE_V1(cfg, BM, BN, WM, WN, NST, BK, FLAGS, caps) case cfg: rc = launch_gemm<BM, BN, WM, WN, NST, BK, FLAGS>(a, splits, s, false); break;
+#define CASE_EIGHT(cfg, ...) case cfg: rc = launch_gemm_8p(a, splits, s); break;
+        CLORA_GEMM_TILES(CASE_RING, CASE_V1, CASE_EIGHT, CASE_NONE, CASE_NONE, CASE_NONE)
+        CLORA_GEMM_PROBE_TILES(CASE_RING)
         default: return CLORA_ERR_ARG;
     }
     if (rc != CLORA_OK) return rc;
@@ -2419,7 +2455,32 @@ extern "C" int clora_gemm_f16_ex(const clora_half* A, int lda, const clora_half*
 
 extern "C" int clora_gemm_ln_fusable(int M, int N, int K, int tile_cfg, int split_k) {
     (void)K;
-    return M > 0 && N == 320 && split_k == 1 && (tile_cfg == 51 || tile_cfg == 52 || tile_cfg == 54 || tile_cfg == 55) ? 1 : 0;
+    const clora_gemm_tile_t& r = tile_row(tile_cfg);
+    return M > 0 && (r.caps & kL) && N == r.bn && split_k == 1 ? 1 : 0;
+}
+
+extern "C" int clora_gemm_tile_info(int tile_cfg, clora_gemm_tile_t* out) {
+    const clora_gemm_tile_t& r = tile_row(tile_cfg);
+    if (!out || &r == &kNoTile) return CLORA_ERR_ARG;
+    *out = r;
+    return CLORA_OK;
+}
+
+extern "C" int clora_gemm_tile_at(int index, clora_gemm_tile_t* out) {
+    if (!out || index < 0 || index >= kNumTileRows) return CLORA_ERR_ARG;
+    *out = kTileRows[index];
+    return CLORA_OK;
+}
+
+// a tile must lie inside one column segment; a tile that cannot carry the down-projection, or does not divide the segment, is replaced:
+// the 8-wave 320-column tiles where the segment allows (128 rows from M = 32768), else 64x64
+extern "C" int clora_gemm_fused_down_tile(int M, int lora_seg, int tile_cfg, int* out) {
+    if (!out || M <= 0 || lora_seg <= 0) return CLORA_ERR_ARG;
+    const clora_gemm_tile_t& r = tile_row(tile_cfg);
+    if ((r.caps & kD) && lora_seg % r.bn == 0) *out = tile_cfg;
+    else if (lora_seg % tile_row(55).bn == 0) *out = M >= 32768 ? 54 : 55;
+    else *out = 43;
+    return CLORA_OK;
 }
 
 extern "C" int clora_finish_deferred(const clora_deferred_t* d, void* stream) {
@@ -2458,10 +2519,11 @@ extern "C" int clora_conv_strip_eligible(int M, int N, const clora_conv_t* conv)
 }
 
 extern "C" int clora_conv_patch_eligible(int M, const clora_conv_t* conv, int tile_cfg) {
-    if (!conv || tile_cfg < 71 || tile_cfg > 79) return 0;
+    const clora_gemm_tile_t& r = tile_row(tile_cfg);
+    if (!conv || !is_patch_tile(r)) return 0;
     GemmArgs a;
     a.M = M; a.conv = *conv;
-    return patch_eligible(a, (tile_cfg == 71 || tile_cfg == 74 || tile_cfg == 79) ? 256 : 128, (tile_cfg == 77 || tile_cfg == 78) ? kPatchWide : 0) ? 1 : 0;   // same arguments as the launcher's switch
+    return patch_eligible(a, r) ? 1 : 0;
 }
 
 extern "C" int clora_gemm_f16(const clora_half* A, int lda, const clora_half* B, clora_half* C, int ldc, int M, int N,

@@ -48,6 +48,7 @@ PROFILER: Optional[KernelProfiler] = None
 _PENDING = {}
 _pending_task = [None]
 FUSE_LN = os.environ.get("CLORA_FUSE_LN", "1") != "0"                 # "0": every LayerNorm is its own launch (round-5 path, A/B runs)
+DEFER_FINISH = os.environ.get("CLORA_DEFER_FINISH", "1") != "0"       # "0": every split-K GEMM runs its own finish pass (A/B runs)
 
 
 class LayerNormSlot:
@@ -57,7 +58,6 @@ class LayerNormSlot:
 
     def __init__(self, gamma, beta, eps):
         self.params, self.out = (gamma, beta, eps), None
-DEFER_FINISH = os.environ.get("CLORA_DEFER_FINISH", "1") != "0"       # "0": every split-K GEMM runs its own finish pass (A/B runs)
 
 
 def flush_pending():
@@ -141,8 +141,27 @@ def workspace(nbytes: int, device) -> torch.Tensor:
 
 _ws_retired = []
 CONV_STRIP = os.environ.get("CLORA_CONV_STRIP", "1") != "0"       # "0": the large-map hint-encoder convolutions stay on the implicit GEMM (A/B)
-WIDE_TILE_CFGS = (1, 4, 7, 8, 9, 21, 31, 41, 53, 56, 58, 59)      # tile_cfg values whose tiles are >= 128 columns wide (GEGLU-forward epilogue)
 GEMM_WS_BYTES = 256 << 20   # split-K slab budget handed to the library's launch planner
+
+
+# ---- the library's tile table (include/clora.h clora_gemm_tile_t): what a tile_cfg is and what it can carry is asked, not listed here
+def gemm_tiles() -> dict:
+    """tile_cfg -> capi.GemmTile, read once per loaded library"""
+    return capi.lib().tiles()
+
+
+def _tile_has(tile_cfg: int, cap: int) -> bool:
+    r = gemm_tiles().get(tile_cfg)
+    return r is not None and bool(r.caps & cap)
+
+
+def fused_down_tile(M: int, lora_seg: int, tile_cfg: int) -> int:
+    """the tile a gemm(..., lora_dpack=, tile_cfg=) launch runs on (clora_gemm_fused_down_tile)"""
+    out = C.c_int()
+    capi.lib().call("clora_gemm_fused_down_tile", M, lora_seg, tile_cfg, C.byref(out))
+    return out.value
+
+
 
 # Autotuned launch configurations (tools/tune_gemm.py on an MI355X): exact-shape lookups for the GEMMs of the
 # SD-1.5 step; any other shape falls back to the library's latency model (split_k = 0, tile_cfg = 0).
@@ -155,11 +174,10 @@ def tuning_key(M, N, K, conv) -> str:
     return f"{M}x{N}x{K}:c{conv.ksize}m{conv.mul}k{conv.kmul}s{conv.shift}e{conv.need_even}h{conv.Hin}"
 
 
-def _tuned(M, N, K, conv):
+def tuned_entry(M, N, K, conv):
     global _TUNING
     if _TUNING is None:
         import json
-        import os
         path = os.environ.get("CLORA_GEMM_TUNING_FILE") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "gemm_tuning_gfx950.json")
         use = os.path.exists(path) and os.environ.get("CLORA_GEMM_TUNING", "1") != "0"   # "0": latency model only (A/B runs)
         _TUNING = json.load(open(path))["table"] if use else {}
@@ -168,7 +186,7 @@ def _tuned(M, N, K, conv):
 
 def _tuned_fused(M, N, K):
     """table entry of a projection launch that carries its adapter's down-projection (key suffix ":x"), or None"""
-    _tuned(M, N, K, None)                                   # loads the table
+    tuned_entry(M, N, K, None)                              # loads the table
     return _TUNING.get(f"{M}x{N}x{K}:x")
 
 
@@ -244,23 +262,23 @@ def gemm(A: torch.Tensor, Bw: torch.Tensor, M: int, N: int, K: int, *, lda: Opti
             and lora_t is None and not defer and ln is None and capi.lib().cdll.clora_conv_strip_eligible(M, N, C.byref(conv))):
         tile_cfg, split_k = 61, 1            # the hint encoder's large-map 3x3 convolutions: strip kernel (include/clora.h)
     if _tuned and split_k == 0 and tile_cfg == 0:
-        hit = globals()["_tuned"](M, N, K, conv)
+        hit = tuned_entry(M, N, K, conv)
         if hit is not None:
             tile_cfg, split_k = hit
     if geglu:
         split_k = 1
-        if geglu == 1 and tile_cfg not in WIDE_TILE_CFGS:
+        if geglu == 1 and not _tile_has(tile_cfg, capi.TILE_CAP_GEGLU):
             tile_cfg = 0                       # the library picks a >= 128-column tile itself
     ws = workspace(GEMM_WS_BYTES if split_k == 0 else max(split_k, 1) * M * N * 4, A.device) if split_k != 1 else None
-    # ln (a LayerNormSlot): where one tile spans the output row (N = 320 on the 8-wave 320-column tiles) the launch also writes
+    # ln (a LayerNormSlot): where one tile spans the output row (N = 320 on the 8-wave 320-column tiles: their L bit) the launch also writes
     # LayerNorm(C) -- the norm that follows an attention out-projection / proj_in in every BasicTransformerBlock -- into ln.out
     # (norms mode: the fused norm would read the rounded C of a launch that also writes its remainder -- the slot is not offered, the
     # caller's norm runs as its own launch on C + c_lo; include/clora.h clora_layernorm_fwd_f16_lo)
     if (ln is not None and ln.out is None and FUSE_LN and not geglu and conv is None and C_ is not None and C_.is_contiguous()
             and not (_TRUNK_NORMS[0] and c_lo is not None)):
         tc = tile_cfg
-        if lora_dpack is not None and tc not in (51, 52, 54, 55) and e.lora_seg % 320 == 0:
-            tc = 54 if M >= 32768 else 55                    # what the library would pick (clora_gemm_f16_ex): made explicit
+        if lora_dpack is not None and not _tile_has(tc, capi.TILE_CAP_LN):
+            tc = fused_down_tile(M, e.lora_seg, 0)           # what the library would pick (clora_gemm_f16_ex): made explicit
         if capi.lib().cdll.clora_gemm_ln_fusable(M, N, K, tc, split_k):
             g_, b_, eps_ = ln.params
             assert g_.dtype == f32 and b_.dtype == f32 and g_.numel() == N and b_.numel() == N
@@ -371,9 +389,6 @@ def trunk_lo_wanted() -> bool:
 
 def trunk_norms_wanted() -> bool:
     return TRUNK_LO_MODE == "norms" and not torch.is_grad_enabled()
-
-
-PATCH_TILE_CFGS = (71, 72, 73, 74, 75, 76, 77, 78, 79)     # conv3x3_patch_kernel variants of clora_gemm_f16_ex (77, 78: 392-pixel patch, rows >= 128 wide; 79: 256x160)
 
 
 def conv_patch_eligible(M: int, conv: ConvDesc, tile_cfg: int) -> bool:

@@ -631,7 +631,6 @@ def _adjacent(ts):
 # every optimizer step -- its flat AdamW kernel updates the weights behind torch's back); an in-place torch update of a
 # parameter is caught by its _version at the point of use.
 FUSE_DOWN = _os.environ.get("CLORA_FUSE_DOWN", "1") != "0"        # "0": separate lora_down launches everywhere (A/B runs)
-FUSE_TILE_N = 320                                                 # column width of the 8-wave tiles that carry the extra rows
 
 
 class _AdapterPacks:
@@ -774,18 +773,26 @@ TRAIN_CONV_PACKS = _TrainConvPacks()
 FUSE_MIN_BLOCKS = int(_os.environ.get("CLORA_FUSE_MIN_BLOCKS", "192"))
 
 
+def _fuse_tile_cols(small=False):
+    """tile_cfg -> columns a segment must be a multiple of, for the tiles that can carry the extra rows (the D bit of the library's tile
+    table); small: only the 4-wave ones"""
+    return K.capi.lib().derived(("fuse_tile_cols", small), lambda L: {
+        c: r.bn for c, r in L.tiles().items() if r.caps & K.capi.TILE_CAP_DPACK and (not small or r.wm * r.wn == 4)})
+
+
+def fuse_tile_n():
+    """column width of the 8-wave tiles that carry the extra rows (the library's own choice where the segment allows)"""
+    return max(_fuse_tile_cols().values())
+
+
 def _fills_the_chip(M, N):
     """the 8-wave 320-column tiles run one block per CU: below ~3/4 of the 256 CUs the narrow 64x64 tiles (3 blocks per CU, 5x the
     blocks) win by more than the separate down-projection launch costs (measured r04: the 16x16 / 32x32 levels lost 0.6 ms/step)"""
-    bm = 128 if M >= 32768 else 64
-    return ((M + bm - 1) // bm) * (N // FUSE_TILE_N) >= FUSE_MIN_BLOCKS
+    r = K.gemm_tiles()[K.fused_down_tile(M, fuse_tile_n(), 0)]
+    return ((M + r.bm - 1) // r.bm) * (N // r.bn) >= FUSE_MIN_BLOCKS
 
 
-SMALL_FUSE_TILES = {21: 128, 41: 128, 22: 64, 42: 64, 26: 64, 23: 64, 43: 64}     # 4-wave BK = 64 tiles that can carry the extra rows: columns
 FUSE_SMALL = _os.environ.get("CLORA_FUSE_SMALL", "1") != "0"                        # "0": only the 8-wave 320-column tiles (A/B runs)
-
-
-_FUSE_TILE_COLS = {**SMALL_FUSE_TILES, 51: 320, 52: 320, 54: 320, 55: 320}      # tile_cfg -> columns a segment must be a multiple of
 
 
 def _fuse_plan(M, N, Kd, seg_w):
@@ -795,12 +802,13 @@ def _fuse_plan(M, N, Kd, seg_w):
     if not FUSE_DOWN or Kd % 64 or seg_w % 64:
         return None
     hx = K._tuned_fused(M, N, Kd)
-    if hx is not None and seg_w % _FUSE_TILE_COLS.get(hx[0], 1 << 30) == 0 and (FUSE_SMALL or hx[0] not in SMALL_FUSE_TILES):
+    small = _fuse_tile_cols(small=True)
+    if hx is not None and seg_w % _fuse_tile_cols().get(hx[0], 1 << 30) == 0 and (FUSE_SMALL or hx[0] not in small):
         return hx[0]
-    if seg_w % FUSE_TILE_N == 0 and _fills_the_chip(M, N):
+    if seg_w % fuse_tile_n() == 0 and _fills_the_chip(M, N):
         return 0
-    hit = K._tuned(M, N, Kd, None) if FUSE_SMALL else None
-    if hit is not None and hit[1] == 1 and hit[0] in SMALL_FUSE_TILES and seg_w % SMALL_FUSE_TILES[hit[0]] == 0:
+    hit = K.tuned_entry(M, N, Kd, None) if FUSE_SMALL else None
+    if hit is not None and hit[1] == 1 and hit[0] in small and seg_w % small[hit[0]] == 0:
         return hit[0]
     return None
 
@@ -1454,7 +1462,7 @@ def control_q_parts(terms, q_downs):
     None where the adapter cannot ride in the GEMM anyway.  Gradients flow through the terms themselves (ops.lora_proj)."""
     outs, jobs = [], []
     for c, D in zip(terms, q_downs):
-        if D.shape[0] != 4 or D.shape[1] % 64 or D.shape[1] % FUSE_TILE_N:
+        if D.shape[0] != 4 or D.shape[1] % 64 or D.shape[1] % fuse_tile_n():
             outs.append(None)
             continue
         T = torch.empty((c.shape[0], 12), dtype=f32, device=c.device)

@@ -134,6 +134,33 @@ typedef struct clora_deferred {
 } clora_deferred_t;
 /* would clora_gemm_f16_ex(..., tile_cfg, split_k) take clora_epilogue_t.ln_out for this shape?  (host-only, no launch) */
 int clora_gemm_ln_fusable(int M, int N, int K, int tile_cfg, int split_k);
+
+/* One row of the library's tile table: what a tile_cfg of clora_gemm_f16_ex is (host-only, no launch).  The table in
+ * csrc/clora_gemm.hip is the single definition: the launcher dispatches from it, and callers that need to know a tile's shape or
+ * what it can carry (tuners, launch planning, tests) ask here instead of keeping lists of their own. */
+enum { CLORA_TILE_RING = 0,         /* gemm_dma_kernel: LDS-DMA ring */
+       CLORA_TILE_V1 = 1,           /* gemm_kernel: the register-staged round-1 loop on the shape of tile_cfg - 10 (A/B runs) */
+       CLORA_TILE_EIGHT_PHASE = 2,  /* gemm_8p_kernel */
+       CLORA_TILE_PATCH = 3,        /* conv3x3_patch_kernel; bm is also the pixel count of its patch */
+       CLORA_TILE_PATCH_WIDE = 4,   /* conv3x3_patch_kernel on the 392-pixel patch (128-pixel rows or row segments) */
+       CLORA_TILE_STRIP = 5 };      /* conv3x3_strip_kernel (no tile shape: clora_conv_strip_eligible) */
+#define CLORA_TILE_CAP_GEGLU 1      /* may run the GEGLU forward epilogue (clora_epilogue_t.geglu == 1) */
+#define CLORA_TILE_CAP_DPACK 2      /* may carry clora_epilogue_t.lora_dpack, for segments that are a multiple of bn */
+#define CLORA_TILE_CAP_LN 4         /* fuses clora_epilogue_t.ln_out at N == bn */
+#define CLORA_TILE_CAP_CONV 8       /* its main loop gathers conv rows (implicit GEMM) */
+typedef struct {
+    int tile_cfg, family;           /* CLORA_TILE_* */
+    int bm, bn, wm, wn;             /* block tile, waves along M x N */
+    int nst, bk, flags;             /* ring stages, K step, main-loop variant (1: fragment reads before the ring refill, 2: round-1 swizzle key) */
+    int caps;                       /* CLORA_TILE_CAP_* bits */
+} clora_gemm_tile_t;
+/* the row of tile_cfg; CLORA_ERR_ARG for a value the library does not know */
+int clora_gemm_tile_info(int tile_cfg, clora_gemm_tile_t* out);
+/* enumeration: row `index` = 0, 1, ... until CLORA_ERR_ARG (no particular order) */
+int clora_gemm_tile_at(int index, clora_gemm_tile_t* out);
+/* the tile a clora_epilogue_t.lora_dpack launch of M rows runs on when asked for tile_cfg: tile_cfg itself if it has the DPACK
+ * bit and lora_seg is a multiple of its bn, else 54 (M >= 32768) / 55 when lora_seg is a multiple of 320, else 43 */
+int clora_gemm_fused_down_tile(int M, int lora_seg, int tile_cfg, int* out);
 /* the plain finish pass for a deferred GEMM (a consumer that cannot fold it, or no consumer at all) */
 int clora_finish_deferred(const clora_deferred_t* d, void* stream);
 
@@ -162,7 +189,7 @@ int clora_gemm_f16(const clora_half* A, int lda, const clora_half* B, clora_half
                    int M, int N, int K, const clora_conv_t* conv, const clora_epilogue_t* epi,
                    int split_k, void* workspace, size_t workspace_bytes, void* stream);
 /* same, with the main-loop variant forced -- tuning / tests (0 = automatic: the library's latency model, or the patch-staged conv
- * kernel for the 3x3 convs it can take).  tile_cfg:
+ * kernel for the 3x3 convs it can take).  tile_cfg, in prose (clora_gemm_tile_info is authoritative):
  *   1-3   128x128 / 128x64 / 64x64 tiles, BK 32, 3-stage LDS-DMA ring        4-6  the same with the deep 5/6/8-stage ring
  *   7, 8  256x128 (wave tile 128x64)                                         9    1 with the round-1 swizzle key (A/B)
  *   11-13 register-staged round-1 loop (A/B)

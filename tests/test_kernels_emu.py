@@ -49,10 +49,7 @@ def test_conv_small_channels():
     KC.case_conv("cpu", 1, 16, 16, 8, 32)       # hint-encoder conv_in shape class (3 -> padded 8 channels)
 
 
-ALL_TILE_CFGS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 21, 22, 23, 26, 31, 32, 33, 41, 42, 43, 51, 52, 53, 54, 55, 56, 57, 58, 59]
-
-
-@pytest.mark.parametrize("tile", ALL_TILE_CFGS)
+@pytest.mark.parametrize("tile", KC.ALL_TILE_CFGS)
 def test_gemm_tile_configs(tile):
     """every main-loop variant (tile shape x ring depth), with ragged M/N/K, split-K and the fused epilogue"""
     KC.case_gemm_plain("cpu", 150, 72, 104, 1, tile_cfg=tile)

@@ -60,10 +60,7 @@ def test_conv_small_channels():
     KC.case_conv(DEV, 1, 64, 64, 8, 32)
 
 
-ALL_TILE_CFGS = [1, 2, 3, 4, 5, 6, 7, 8, 9, 21, 22, 23, 26, 31, 32, 33, 41, 42, 43, 51, 52, 53, 54, 55, 56, 57, 58, 59]
-
-
-@pytest.mark.parametrize("tile", ALL_TILE_CFGS)
+@pytest.mark.parametrize("tile", KC.ALL_TILE_CFGS)
 def test_gemm_tile_configs(tile):
     """every main-loop variant (tile shape x ring depth), with ragged M/N/K, split-K and the fused epilogue"""
     KC.case_gemm_plain(DEV, 1000, 328, 1256, 1, tile_cfg=tile)

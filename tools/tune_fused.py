@@ -57,7 +57,7 @@ def timeit(fn, iters=10, warm=2):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / (2 * iters) * 1e3
 
-TILES = {51: 320, 52: 320, 54: 320, 55: 320, 21: 128, 41: 128, 22: 64, 42: 64, 26: 64, 23: 64, 43: 64}
+TILES = ops._fuse_tile_cols()          # tile_cfg -> columns a segment must be a multiple of: the tiles that can carry the down-projection
 path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "controllora_amd", "gemm_tuning_gfx950.json")
 doc = json.load(open(path))
 table = doc["table"]
@@ -89,7 +89,7 @@ for (M, N, Kd, seg, u_tr, has_b, has_r, has_tin), cnt in sorted(seen.items(), ke
         res[tile] = us
         if best is None or us < best[0]:
             best = (us, tile)
-    cur_tile = cur if cur else (54 if M >= 32768 else 55)
+    cur_tile = cur if cur else K.fused_down_tile(M, ops.fuse_tile_n(), 0)          # 0 / None: the library's own wide choice
     cur_us = res.get(cur_tile, best[0])
     tot_cur += cnt * cur_us; tot_best += cnt * best[0]
     table[f"{M}x{N}x{Kd}:x"] = [best[1], 1]

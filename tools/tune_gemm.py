@@ -94,7 +94,11 @@ def timeit(fn, iters=10, warm=2):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / (2 * iters) * 1e3
 
-CFGS = [1, 2, 3, 4, 5, 6, 7, 8, 21, 22, 23, 26, 31, 32, 33, 41, 42, 43, 51, 52, 53, 54, 55, 56, 57, 58, 71, 72, 73, 74, 75, 76, 79]
+# every tile of the library's table but the A/B-only ones: the round-1 swizzle key and register-staged loop, the eight-phase kernel, the
+# strip kernel (chosen by eligibility, not by timing) and the wide-patch tiles (profiles/r03_vae_conv_ab.txt)
+WIDE_TILE_CFGS = {c for c, r in K.gemm_tiles().items() if r.caps & K.capi.TILE_CAP_GEGLU}       # tiles that run the GEGLU-forward epilogue
+PATCH_TILE_CFGS = {c for c, r in K.gemm_tiles().items() if r.family in (K.capi.TILE_PATCH, K.capi.TILE_PATCH_WIDE)}      # conv3x3_patch_kernel variants
+CFGS = [c for c, r in sorted(K.gemm_tiles().items()) if r.family in (K.capi.TILE_RING, K.capi.TILE_PATCH) and r.flags != 2]
 if args.cfgs:
     CFGS = [int(c) for c in args.cfgs.split(",")]
 path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "controllora_amd", "gemm_tuning_gfx950.json")
@@ -135,7 +139,7 @@ for (M, N, Kd, ck), cnt in sorted(seen.items(), key=lambda kv: -kv[0][0] * kv[0]
     elif args.geglu:
         del A, Bw, out, res_
         continue
-    if (args.patch_only and not (conv is not None and any(K.conv_patch_eligible(M, conv, c) for c in K.PATCH_TILE_CFGS))) or \
+    if (args.patch_only and not (conv is not None and any(K.conv_patch_eligible(M, conv, c) for c in PATCH_TILE_CFGS))) or \
             (args.plain_only and conv is not None):
         del A, Bw, out, res_
         continue
@@ -148,15 +152,15 @@ for (M, N, Kd, ck), cnt in sorted(seen.items(), key=lambda kv: -kv[0][0] * kv[0]
     r01 = None
     geglu_sig = (M, N, Kd, ck) in wide_only
     for tile in CFGS:
-        if geglu_sig and tile not in K.WIDE_TILE_CFGS:
+        if geglu_sig and tile not in WIDE_TILE_CFGS:
             continue
-        if tile in K.PATCH_TILE_CFGS and not (conv is not None and K.conv_patch_eligible(M, conv, tile)):
+        if tile in PATCH_TILE_CFGS and not (conv is not None and K.conv_patch_eligible(M, conv, tile)):
             continue                                       # would only re-time the fallback
         prev = None
         for sk in (1, 2, 3, 4, 6, 8, 12, 16):
             if sk > 1 and (geglu_sig or (gm is not None and args.geglu) or (Kd // 32) // sk < 4 or sk * M * N * 4 > K.GEMM_WS_BYTES or M * N > 16384 * 1280):
                 break
-            if tile in K.PATCH_TILE_CFGS and sk > conv.Cin // 64:
+            if tile in PATCH_TILE_CFGS and sk > conv.Cin // 64:
                 break
             try:
                 us = timeit(lambda: run(sk, tile), iters=iters)
