@@ -188,6 +188,7 @@ _PROTOS = {
     "clora_pool2x2_sum_f16": [_P, _P, _I, _I, _I, _I, _P],
     "clora_colsum_f16": [_P, _I, _P, _I, _I, _P],
     "clora_mse_f16": [_P, _P, _P, _P, _Z, _F, _P, _P],
+    "clora_mse_weighted_f16": [_P, _P, _P, _P, _P, _I, _Z, _F, _P, _P],
     "clora_cast_f32_to_f16": [_P, _P, _Z, _P],
     "clora_cast_f16_to_f32": [_P, _P, _Z, _P],
     "clora_grad_sumsq_f32": [_P, _Z, _P, _P],

@@ -166,6 +166,41 @@ __global__ __launch_bounds__(256) void mse_kernel(const half_t* pred, const half
     if (threadIdx.x == 0) atomicAdd(loss_sum, red[0] + red[1] + red[2] + red[3]);
 }
 
+// Per-sample-weighted MSE (DreamBooth's prior-preservation loss: mse(instance) + w * mse(prior) is one launch with weights
+// [1.., w..]).  blockIdx.y walks the samples, blockIdx.x the 16-byte vectors of one sample, so a block only ever adds up one
+// sample: per-thread partial -> wave -> block -> ONE atomic per block and sample.  At most two blocks work on a sample, so a
+// sum that starts at zero is bit-reproducible (two fp32 additions commute; three would not).  The seed keeps mse_kernel's
+// association ((grad_scale * loss_scale) * weight) * d, so that with every weight 1.0 it is bit-identical to mse_kernel's.
+__global__ __launch_bounds__(256) void mse_weighted_kernel(const half_t* pred, const half_t* target, const float* weights,
+                                                           float* sample_sums, half_t* dpred, int B, size_t n8_per_sample,
+                                                           float grad_scale, const float* loss_scale) {
+    __shared__ float red[4];
+    const float gs = loss_scale ? grad_scale * loss_scale[0] : grad_scale;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+        const float gw = gs * weights[b];
+        const size_t base = (size_t)b * n8_per_sample;
+        float acc = 0.f;
+        EW_LOOP(i, n8_per_sample) {
+            const half8 a = ld8(pred + (base + i) * 8), t = ld8(target + (base + i) * 8);
+            half8 o;
+            float sq[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = (float)a[e] - (float)t[e];
+                sq[e] = d * d;
+                o[e] = (half_t)(gw * d);
+            }
+            acc += ((sq[0] + sq[1]) + (sq[2] + sq[3])) + ((sq[4] + sq[5]) + (sq[6] + sq[7]));   // one serial add per vector
+            if (dpred) st8(dpred + (base + i) * 8, o);
+        }
+        acc = wave_sum(acc);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) atomicAdd(sample_sums + b, (red[0] + red[1]) + (red[2] + red[3]));
+        __syncthreads();                      // red[] is written again for the next sample of this block
+    }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_f16_kernel(const float* x, half_t* y, size_t n) {
     EW_LOOP(i, n) y[i] = (half_t)x[i];
 }
@@ -324,6 +359,18 @@ extern "C" int clora_mse_f16(const clora_half* pred, const clora_half* target, f
     if (blocks > 256) blocks = 256;
     hipLaunchKernelGGL(mse_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, H(pred), H(target), loss_sum, HM(dpred),
                        n / 8, grad_scale, loss_scale);
+    return clora_check_launch();
+}
+extern "C" int clora_mse_weighted_f16(const clora_half* pred, const clora_half* target, const float* weights, float* sample_sums,
+                                      clora_half* dpred, int B, size_t n_per_sample, float grad_scale, const float* loss_scale,
+                                      void* stream) {
+    if (!pred || !target || !weights || !sample_sums || B <= 0 || n_per_sample == 0 || (n_per_sample & 7)) return CLORA_ERR_ARG;
+    // two blocks per sample once there is more than one block's worth of vectors (see the kernel: reproducible sums); a thread's
+    // serial chain is one addition per vector it visits, 4 at the 512x512 latent (n_per_sample 16384)
+    const int bx = n_per_sample / 8 > 256 ? 2 : 1;
+    const int by = B < 1024 ? B : 1024;
+    hipLaunchKernelGGL(mse_weighted_kernel, dim3(bx, by), dim3(256), 0, (hipStream_t)stream, H(pred), H(target), weights, sample_sums,
+                       HM(dpred), B, n_per_sample / 8, grad_scale, loss_scale);
     return clora_check_launch();
 }
 extern "C" int clora_cast_f32_to_f16(const float* x, clora_half* y, size_t n, void* stream) {

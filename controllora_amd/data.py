@@ -6,6 +6,7 @@ image / guide / caption triples -> `pixel_values`, `guide_values` in [-1, 1] and
   dataset is reachable offline, so this is what bench/tests/smoke train on.
 * `ImageGuideDataset` -- wraps a HuggingFace `datasets` split or an image folder with the reference's transform:
   bilinear resize of the short side to `resolution`, ToTensor, Normalize(0.5, 0.5), one shared random crop.
+* `DreamBoothDataset` / `dreambooth_collate` -- instance (+ class) image folders of train_dreambooth_lora.py.
 """
 from __future__ import annotations
 
@@ -80,6 +81,70 @@ class ImageGuideDataset(torch.utils.data.Dataset):
                 "input_ids": self.tokenizer([cap])[0]}
 
 
+class DreamBoothDataset(torch.utils.data.Dataset):
+    """Instance images with the instance prompt and, for prior preservation, class images with the class prompt (reference
+    train_dreambooth_lora.py:410-488).  Length max(#class, #instance), both folders indexed modulo their size (files in sorted
+    order).  Transform: short side bilinearly resized to `size` (PIL, as ImageGuideDataset), centre crop or a random crop
+    drawn from torch's global generator (torchvision's RandomCrop draws: top, then left), scaled to [-1, 1]."""
+
+    def __init__(self, instance_data_root, instance_prompt, tokenizer, class_data_root=None, class_prompt=None, size=512,
+                 center_crop=False):
+        import os
+        self.size, self.center_crop, self.tokenizer = size, center_crop, tokenizer
+        if not os.path.isdir(instance_data_root):
+            raise ValueError("Instance images root doesn't exists.")
+        self.instance_images_path = sorted(os.path.join(instance_data_root, f) for f in os.listdir(instance_data_root))
+        self.num_instance_images = len(self.instance_images_path)
+        if self.num_instance_images == 0:
+            raise ValueError(f"no instance images under {instance_data_root}")
+        self.instance_prompt, self.class_prompt = instance_prompt, class_prompt
+        self._length = self.num_instance_images
+        self.class_data_root = class_data_root
+        if class_data_root is not None:
+            os.makedirs(class_data_root, exist_ok=True)
+            self.class_images_path = sorted(os.path.join(class_data_root, f) for f in os.listdir(class_data_root))
+            self.num_class_images = len(self.class_images_path)
+            self._length = max(self.num_class_images, self.num_instance_images)
+
+    def __len__(self):
+        return self._length
+
+    def _image(self, path) -> torch.Tensor:
+        from PIL import Image
+        t = _to_tensor_resized(Image.open(path), self.size)
+        _, h, w = t.shape
+        if self.center_crop:
+            y1, x1 = int(round((h - self.size) / 2.0)), int(round((w - self.size) / 2.0))
+        elif h == self.size and w == self.size:
+            y1 = x1 = 0
+        else:
+            y1 = int(torch.randint(0, h - self.size + 1, (1,)))
+            x1 = int(torch.randint(0, w - self.size + 1, (1,)))
+        return t[:, y1:y1 + self.size, x1:x1 + self.size].contiguous()
+
+    def __getitem__(self, index):
+        index = int(index)
+        ex = {"instance_images": self._image(self.instance_images_path[index % self.num_instance_images]),
+              "instance_prompt_ids": self.tokenizer([self.instance_prompt])[:1]}
+        if self.class_data_root is not None:
+            if self.num_class_images == 0:
+                raise ValueError(f"no class images under {self.class_data_root}")
+            ex["class_images"] = self._image(self.class_images_path[index % self.num_class_images])
+            ex["class_prompt_ids"] = self.tokenizer([self.class_prompt])[:1]
+        return ex
+
+
+def dreambooth_collate(examples: List[dict], with_prior_preservation: bool = False) -> Dict[str, torch.Tensor]:
+    """instance examples first, then the class examples of the same items: the batch is [inst..., class...] so that one UNet
+    pass serves both losses (reference train_dreambooth_lora.py:491-510)"""
+    ids = [e["instance_prompt_ids"] for e in examples]
+    pix = [e["instance_images"] for e in examples]
+    if with_prior_preservation:
+        ids += [e["class_prompt_ids"] for e in examples]
+        pix += [e["class_images"] for e in examples]
+    return {"input_ids": torch.cat(ids, 0), "pixel_values": torch.stack(pix).contiguous().float()}
+
+
 def collate(examples: List[dict]) -> Dict[str, torch.Tensor]:
     out = {"pixel_values": torch.stack([e["pixel_values"] for e in examples]).float()}
     if "guide_values" in examples[0]:
@@ -93,7 +158,9 @@ def collate(examples: List[dict]) -> Dict[str, torch.Tensor]:
 
 
 # ---- LR schedules (diffusers.optimization.get_scheduler names accepted by --lr_scheduler) as multipliers of the base LR
-def lr_lambda(name: str, warmup: int, total: int, cycles: float = 0.5, power: float = 1.0) -> Callable[[int], float]:
+def lr_lambda(name: str, warmup: int, total: int, cycles: float = 0.5, power: float = 1.0, restarts: int = 1) -> Callable[[int], float]:
+    """cycles: of "cosine" (get_scheduler never passes one: always 0.5); restarts: `num_cycles` of "cosine_with_restarts"
+    (--lr_num_cycles of train_dreambooth_lora.py); power: of "polynomial" (--lr_power)"""
     warm = lambda s: float(s) / float(max(1, warmup))
     if name == "constant":
         return lambda s: 1.0
@@ -105,7 +172,7 @@ def lr_lambda(name: str, warmup: int, total: int, cycles: float = 0.5, power: fl
         return lambda s: warm(s) if s < warmup else max(
             0.0, 0.5 * (1.0 + math.cos(math.pi * cycles * 2.0 * float(s - warmup) / float(max(1, total - warmup)))))
     if name == "cosine_with_restarts":
-        def f(s, n=1):
+        def f(s, n=restarts):
             if s < warmup:
                 return warm(s)
             p = float(s - warmup) / float(max(1, total - warmup))

@@ -1014,6 +1014,17 @@ def mse(pred, target, loss_sum, dpred, grad_scale, loss_scale=None):
           pred.numel(), float(grad_scale), ptr(loss_scale, f32) if loss_scale is not None else None)
 
 
+def mse_weighted(pred, target, weights, sample_sums, dpred, grad_scale, loss_scale=None):
+    """per-sample-weighted MSE over [B, ...] tensors: sample_sums[b] += sum d^2 (unweighted), dpred = grad_scale * loss_scale *
+    weights[b] * d (include/clora.h clora_mse_weighted_f16); weights / sample_sums fp32 [B] on the tensors' device"""
+    B = int(weights.numel())
+    if B <= 0 or sample_sums.numel() != B or pred.numel() != target.numel() or pred.numel() % B:
+        raise capi.CloraError(f"mse_weighted: {pred.numel()} elements, {B} weights, {sample_sums.numel()} sums")
+    _call("clora_mse_weighted_f16", ptr(pred, f16), ptr(target, f16), ptr(weights, f32), ptr(sample_sums, f32),
+          ptr(dpred, f16) if dpred is not None else None, B, pred.numel() // B, float(grad_scale),
+          ptr(loss_scale, f32) if loss_scale is not None else None)
+
+
 def grad_sumsq(g, state):
     _call("clora_grad_sumsq_f32", ptr(g, f32), g.numel(), ptr(state, f32))
 

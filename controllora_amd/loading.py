@@ -124,3 +124,45 @@ def load_lora_attn_procs(unet, path_or_state_dict) -> dict:
         _load_into(proc, {part: sd[f"{n}.{part}"] for part in _LORA_PARTS})
         procs[n] = proc.to(dev)
     return procs
+
+
+LORA_WEIGHT_NAME, LORA_WEIGHT_NAME_SAFE = "pytorch_lora_weights.bin", "pytorch_lora_weights.safetensors"
+
+
+def lora_state_dict(unet_or_procs) -> dict:
+    """{`<site>.processor.to_{q,k,v,out}_lora.{down,up}.weight`: fp32 CPU tensor} of plain LoRA processors: a UNet (its
+    `attn_processors`), a {processor name: processor} dict or a `train.AttnProcsLayers`"""
+    from . import models
+    if hasattr(unet_or_procs, "attn_processors"):
+        procs = unet_or_procs.attn_processors
+    elif hasattr(unet_or_procs, "named_processors"):
+        procs = unet_or_procs.named_processors()
+    else:
+        procs = dict(unet_or_procs)
+    sd = {}
+    for n, proc in procs.items():
+        if type(proc) is not models.LoRACrossAttnProcessor or proc.post_add:
+            raise ValueError(f"{n}: {type(proc).__name__} is not a plain LoRA processor; the diffusers LoRA file holds nothing else")
+        own = proc.state_dict()
+        miss = [part for part in _LORA_PARTS if part not in own]
+        if miss:
+            raise ValueError(f"{n}: the processor has no {miss[0]} (a skipped segment cannot be written to a LoRA file)")
+        for part in _LORA_PARTS:
+            sd[f"{n}.{part}"] = own[part].detach().to("cpu", torch.float32).contiguous().clone()
+    return sd
+
+
+def save_lora_attn_procs(unet_or_procs, directory: str, weights_name: str = None, safe_serialization: bool = False) -> str:
+    """Write the file `load_lora_attn_procs` reads (what the reference's `unet.save_attn_procs` writes,
+    train_dreambooth_lora.py:986-994): `pytorch_lora_weights.bin` (torch.save) or `.safetensors`.  -> the path written"""
+    sd = lora_state_dict(unet_or_procs)
+    os.makedirs(directory, exist_ok=True)
+    if weights_name is None:
+        weights_name = LORA_WEIGHT_NAME_SAFE if safe_serialization else LORA_WEIGHT_NAME
+    path = os.path.join(directory, weights_name)
+    if safe_serialization or weights_name.endswith(".safetensors"):
+        from safetensors.torch import save_file
+        save_file(sd, path)
+    else:
+        torch.save(sd, path)
+    return path

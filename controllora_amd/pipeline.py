@@ -11,7 +11,7 @@ from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 
 @torch.no_grad()
 def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guidance_scale=9.0, latents=None,
-                generator=None, sampler="ddim", graph=None, cache_text_kv=True, callback=None):
+                generator=None, sampler="ddim", graph=None, cache_text_kv=True, callback=None, size=None):
     """guide [Bc,3,H,W] (control batch 1 broadcasts over the CFG batch, quirk C6); cond/uncond [B,77,768].
     sampler: "ddim" (BASELINE inference config) or "dpm" (DPM-Solver++(2M), what the reference apps select).
 
@@ -21,11 +21,22 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
     timestep).  graph: replay ONE captured hipGraph of the UNet forward per step (default: on a GPU); the timestep lives
     in a device tensor, so all steps replay the same graph (default: on a GPU when steps >= 8).
     callback(i, latents, eps): called after scheduler step i = 1..steps (tests record the trajectory with it).
+    Without a control model (`control_lora=None`, plain text-to-image) `guide` may be None: `size` = (height, width) of the image
+    in pixels, or `latents`, then gives the latent size.
     Returns the denoised latents in **fp32** (the scheduler state is kept in fp32 between steps)."""
     from . import models
     B = cond_emb.shape[0]
     dev = cond_emb.device
-    H, W = guide.shape[2] // 8, guide.shape[3] // 8
+    if guide is not None:
+        H, W = guide.shape[2] // 8, guide.shape[3] // 8
+    elif control_lora is not None:
+        raise ValueError("a control model needs a guide image")
+    elif latents is not None:
+        H, W = latents.shape[2], latents.shape[3]
+    elif size is not None:
+        H, W = int(size[0]) // 8, int(size[1]) // 8
+    else:
+        raise ValueError("without a guide, give the image size (size=(height, width)) or the initial latents")
     sched = DDIMScheduler() if sampler == "ddim" else DPMSolverMultistepScheduler()
     sched.set_timesteps(steps)
     if latents is None:
@@ -97,8 +108,9 @@ class ControlLoRAPipeline:
         unet = loading.load_unet(base, dev)
         if isinstance(control_lora, str):
             control_lora = models.ControlLoRA.from_pretrained(control_lora)
-        control_lora = control_lora.to(dev)
-        unet.set_attn_processor(models.map_processors_to_unet(unet, control_lora))
+        if control_lora is not None:                   # None: the frozen base model alone, plain text-to-image
+            control_lora = control_lora.to(dev)
+            unet.set_attn_processor(models.map_processors_to_unet(unet, control_lora))
         return cls(unet, control_lora, loading.load_vae(base, dev), text.load_text_encoder(base, dev, small=base.endswith("small")),
                    text.load_tokenizer(base))
 
@@ -108,19 +120,27 @@ class ControlLoRAPipeline:
         return self.text_encoder(self.tokenizer(list(prompts)).to(dev))[0].half()
 
     @torch.no_grad()
-    def __call__(self, prompt, guide, a_prompt="", n_prompt="", num_samples=1, ddim_steps=50, scale=9.0, seed=None,
-                 output_type="uint8", sampler="ddim"):
+    def __call__(self, prompt, guide=None, a_prompt="", n_prompt="", num_samples=1, ddim_steps=50, scale=9.0, seed=None,
+                 output_type="uint8", sampler="ddim", height=None, width=None):
         """guide: float tensor [1, 3, H, W] (broadcast over the samples) or [num_samples, 3, H, W] (one guide per image), in
         [-1, 1]; H, W multiples of 64, square or not -- every size the reference apps' image_resolution slider gives (256 ... 768):
-        the UNet's and the VAE's attention are flash kernels that take any number of tokens"""
+        the UNet's and the VAE's attention are flash kernels that take any number of tokens.
+        A pipeline without a control model takes no guide: `height` / `width` (multiples of 64, default 512) size the image."""
+        if guide is None:
+            if self.control_lora is not None:
+                raise ValueError("this pipeline has a control model: it needs a guide image")
+            height, width = int(height or width or 512), int(width or height or 512)
+            if height % 64 or width % 64:
+                raise ValueError(f"height / width must be multiples of 64, got {height} x {width}")
         dev = next(self.text_encoder.parameters()).device
         gen = torch.Generator(device=dev)
         if seed is not None:
             gen.manual_seed(int(seed))
         cond = self.encode_prompt([prompt + (", " + a_prompt if a_prompt else "")] * num_samples)
         uncond = self.encode_prompt([n_prompt] * num_samples)
-        lat = ddim_sample(self.unet, self.control_lora, guide.to(dev).half(), cond, uncond, steps=ddim_steps,
-                          guidance_scale=scale, generator=gen, sampler=sampler)
+        lat = ddim_sample(self.unet, self.control_lora, None if guide is None else guide.to(dev).half(), cond, uncond,
+                          steps=ddim_steps, guidance_scale=scale, generator=gen, sampler=sampler,
+                          size=None if guide is not None else (height, width))
         img = self.vae.decode(lat.half() / self.vae.scaling_factor).sample.float().clamp(-1, 1)
         if output_type == "uint8":
             return ((img.permute(0, 2, 3, 1) + 1.0) * 127.5).round().to(torch.uint8).cpu()

@@ -323,6 +323,10 @@ class ControlLoRATrainer:
         for dst, src in zip(self._static, (noisy_latents, timesteps, encoder_hidden_states, guide, target)):
             if src is not None and src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)
+        return self._replay_step()
+
+    def _replay_step(self):
+        """the captured step on whatever the static input buffers hold now"""
         assert self.accum == 1, "the captured step assumes one micro-batch per optimizer step"
         self._reduced = False
         self._g_fb.replay()
@@ -500,3 +504,149 @@ class ControlLoRATrainer:
         """flat gradient in ``control_lora.parameters()`` order (what the reference / oracle would concatenate)"""
         return torch.cat([p.grad.reshape(-1) for p in self.control_lora.parameters() if p.requires_grad]) / (
             self.state[3] * (self.world if self._reduced else 1))
+
+
+class AttnProcsLayers(nn.Module):
+    """The attention processors of a UNet as one module, in `unet.attn_processors` order (reference
+    train_dreambooth_lora.py:723 `AttnProcsLayers(unet.attn_processors)`): what a plain-LoRA run optimises and checkpoints.
+    `names[i]` is the processor name (`<site>.processor`) of `layers[i]`."""
+
+    def __init__(self, attn_processors: Dict[str, nn.Module]):
+        super().__init__()
+        bad = [n for n, p in attn_processors.items() if not isinstance(p, nn.Module)]
+        if bad:
+            raise ValueError(f"attention processors without weights cannot be trained: {bad[:4]}")
+        self.names = list(attn_processors.keys())
+        self.layers = nn.ModuleList(attn_processors.values())
+
+    def named_processors(self) -> Dict[str, nn.Module]:
+        return dict(zip(self.names, self.layers))
+
+
+class LoRATrainer(ControlLoRATrainer):
+    """The same device-resident step for plain LoRA processors on every attention site (reference train_dreambooth_lora.py:
+    859-920): no hint encoder and no guide; the trainables are an `AttnProcsLayers`.  With `sample_weights` (fp32 [B] on the
+    device) the loss is DreamBooth's prior-preservation loss, mse(first half) + w * mse(second half), as ONE weighted launch:
+    weights [1] * B/2 + [w] * B/2 (:898-910).  Optimizer, accumulation, LR multiplier, exchange paths and the optimizer graph
+    are ControlLoRATrainer's, unchanged."""
+
+    def __init__(self, unet, lora_layers, **kw):
+        super().__init__(unet, lora_layers, **kw)
+        self.lora_layers = lora_layers
+        # fp32 [B] per-sample sums of squared errors, ONE buffer per batch size, created on first use and never freed or rebound:
+        # a captured graph holds the address of the one it was captured with, and eager steps of another batch size (the short
+        # last batch of an epoch) between replays get a buffer of their own
+        self._sums = {}
+        self._last = None                        # (weights or None, (B, n_per_sample)) of the step the loss scalars describe
+        self._captured = None                    # the same record for the captured step
+
+    @property
+    def sample_sums(self):
+        """per-sample sums of the last weighted micro-batch (None before one)"""
+        if self._last is None or self._last[0] is None:
+            return None
+        return self._sums[self._last[1][0]]
+
+    def forward_backward(self, noisy_latents, timesteps, encoder_hidden_states, target, sample_weights=None):
+        K.lora_wgrad_discard()
+        if self._micro == 0:
+            self.flat.zero_grad()
+            self._reduced = False
+        self.loss_sum.zero_()
+        pred = self.unet(noisy_latents, timesteps, encoder_hidden_states).sample
+        pred_c = pred.contiguous()
+        dpred = torch.empty_like(pred_c)
+        n, B = pred_c.numel(), pred_c.shape[0]
+        tgt = target.to(f16).contiguous()
+        if sample_weights is None:
+            K.mse(pred_c, tgt, self.loss_sum, dpred, 2.0 / n / self.accum, self.state[3:4])
+        else:
+            if sample_weights.dtype != f32 or sample_weights.numel() != B or B % 2:
+                raise ValueError(f"sample_weights: expected fp32 [{B}] for an even batch [instance..., prior...], got "
+                                 f"{sample_weights.dtype} {tuple(sample_weights.shape)}")
+            if B not in self._sums:
+                if pred_c.is_cuda and torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("the per-sample sums of this batch size must exist before a capture (capture() warms up first)")
+                self._sums[B] = torch.zeros(B, dtype=f32, device=pred_c.device)
+            sums = self._sums[B]
+            sums.zero_()
+            # each half is a mean over its own B/2 samples (two F.mse_loss calls), so the seed divides by n_per_sample * B/2
+            K.mse_weighted(pred_c, tgt, sample_weights, sums, dpred, 2.0 / ((n // B) * (B // 2)) / self.accum, self.state[3:4])
+        self._last = (sample_weights, (B, n // B))
+        pred_c.backward(dpred)
+        K.lora_wgrad_flush()
+        return pred
+
+    def step(self, noisy_latents, timesteps, encoder_hidden_states, target, sample_weights=None):
+        pred = self.forward_backward(noisy_latents, timesteps, encoder_hidden_states, target, sample_weights)
+        self.optimizer_step()
+        return pred
+
+    def capture(self, noisy_latents, timesteps, encoder_hidden_states, target, sample_weights=None, warmup=2):
+        """ControlLoRATrainer.capture without the guide; the weights are a static device tensor (`_static_weights`)"""
+        self._static = [t.clone() for t in (noisy_latents, timesteps, encoder_hidden_states, target)]
+        self._static_weights = None if sample_weights is None else sample_weights.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(warmup):
+                self.forward_backward(*self._static, self._static_weights)
+                self.optimizer_step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        self._g_fb = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._g_fb):
+            self._static_pred = self.forward_backward(*self._static, self._static_weights)
+        self._captured = self._last              # the replayed graph writes this record's buffers, whatever ran eagerly in between
+        self._capture_optimizer_graph()
+        return self
+
+    def step_graphed(self, noisy_latents=None, timesteps=None, encoder_hidden_states=None, target=None):
+        for dst, src in zip(self._static, (noisy_latents, timesteps, encoder_hidden_states, target)):
+            if src is not None and src.data_ptr() != dst.data_ptr():
+                dst.copy_(src, non_blocking=True)
+        pred = self._replay_step()
+        self._last = self._captured              # loss() / loss_parts() describe the replayed step again
+        return pred
+
+    # -- host-visible scalars (each forces a sync).  They describe the LAST micro-batch, eager or replayed.
+    def _last_step(self, what):
+        if self._last is None:
+            raise RuntimeError(f"{what} describes the last step: run forward_backward / step / step_graphed first")
+        return self._last
+
+    def loss_parts(self):
+        """(instance loss, prior loss) of the last weighted micro-batch: the two plain means of the reference (:904, :907)"""
+        weights, (B, nps) = self._last_step("loss_parts()")
+        if weights is None:
+            raise RuntimeError("loss_parts() needs a step with sample_weights")
+        sums = self._sums[B].double().cpu()
+        return float(sums[:B // 2].sum()) / (nps * (B // 2)), float(sums[B // 2:].sum()) / (nps * (B // 2))
+
+    def loss(self, numel=None) -> float:
+        """instance + w * prior after a weighted step (w read from the weights), the plain mean otherwise.  `numel` is optional:
+        the trainer knows the size of the batch it saw; a value that is not that size is an error, not another divisor."""
+        weights, (B, nps) = self._last_step("loss()")
+        if numel is not None and int(numel) != B * nps:
+            raise ValueError(f"loss(numel={numel}): the last step saw {B} x {nps} = {B * nps} elements")
+        if weights is None:
+            return float(self.loss_sum) / (B * nps)
+        return float((self._sums[B].double() * weights.double()).sum()) / (nps * (B // 2))
+
+    # -- checkpoints: the flat trainer state plus the LoRA file every consumer of this repository reads
+    def save_state(self, directory: str) -> None:
+        import os
+        from safetensors.torch import save_file
+        from . import loading
+        os.makedirs(directory, exist_ok=True)
+        save_file(self.state_dict(), os.path.join(directory, "trainer_state.safetensors"))
+        loading.save_lora_attn_procs(self.lora_layers, directory, safe_serialization=True)
+
+    def load_state(self, directory: str) -> None:
+        import os
+        from safetensors.torch import load_file
+        own = os.path.join(directory, "trainer_state.safetensors")
+        if not os.path.exists(own):
+            raise FileNotFoundError(f"{own}: a plain-LoRA checkpoint is the directory LoRATrainer.save_state writes "
+                                    "(the accelerate layout is not read by this trainer)")
+        self.load_state_dict(load_file(own))

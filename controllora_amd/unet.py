@@ -474,6 +474,28 @@ class UNet2DConditionModel(nn.Module):
                              f"not match the number of attention layers: {count}.")
         self._walk_attn(lambda n, m: m.set_processor(processor[n] if isinstance(processor, dict) else processor))
 
+    def save_attn_procs(self, save_directory, weights_name=None, save_function=None, safe_serialization=None):
+        """the plain LoRA processors of every site as one diffusers-format file (reference train_dreambooth_lora.py:986-994:
+        `weights_name` picks the file, `save_function` -- torch.save or safetensors' save_file -- the format)"""
+        from . import loading
+        if safe_serialization is None:
+            safe_serialization = (weights_name or "").endswith(".safetensors") or \
+                getattr(save_function, "__module__", "").startswith("safetensors")
+        if weights_name is None:
+            weights_name = loading.LORA_WEIGHT_NAME_SAFE if safe_serialization else loading.LORA_WEIGHT_NAME
+        if save_function is None:
+            return loading.save_lora_attn_procs(self, save_directory, weights_name, safe_serialization)
+        import os
+        os.makedirs(save_directory, exist_ok=True)
+        path = os.path.join(save_directory, weights_name)
+        save_function(loading.lora_state_dict(self), path)
+        return path
+
+    def load_attn_procs(self, path_or_state_dict):
+        """install the plain LoRA processors of a diffusers-format file / folder / state dict (reference :1005)"""
+        from . import loading
+        self.set_attn_processor(loading.load_lora_attn_procs(self, path_or_state_dict))
+
     # ---- forward
     def time_embed(self, timestep, batch, device):
         if not torch.is_tensor(timestep):

@@ -610,6 +610,18 @@ int clora_colsum_f16(const clora_half* A, int lda, float* out, int M, int N, voi
  * (F.mse_loss in fp32 + the GradScaler-scaled backward seed, train...:783,790; loss_scale is device resident) */
 int clora_mse_f16(const clora_half* pred, const clora_half* target, float* loss_sum, clora_half* dpred, size_t n,
                   float grad_scale, const float* loss_scale, void* stream);
+/* the same loss with one weight per sample (DreamBooth prior preservation, reference train_dreambooth_lora.py:898-912:
+ * mse(instance) + w * mse(prior) = weights [1.., w..] and grad_scale 2 / (n_per_sample * B_instance)), d = pred - target in fp32:
+ *   sample_sums[b] += sum_i d[b, i]^2                      (unweighted: the two losses can be reported separately)
+ *   dpred[b, i]     = ((grad_scale * loss_scale[0]) * weights[b]) * d[b, i]     (dpred may be NULL: loss only)
+ * With every weight 1.0 dpred is bit-identical to clora_mse_f16 over the same B * n_per_sample elements.  n_per_sample % 8 == 0.
+ * weights, sample_sums and loss_scale are device resident; one launch, no host sync, no allocation.
+ * Intended range: loss tensors of latent size, n_per_sample up to about 131,072 (4 x 64 x 64 = 16,384 at 512 x 512).  At most two
+ * workgroups work on a sample, whatever its size (a sum that starts at zero is then bit-reproducible), so a thread's serial fp32
+ * chain is n_per_sample / 4096 additions and one huge sample would run on two compute units: correct, but neither fast nor as
+ * accurate as a wide reduction.  Use clora_mse_f16 for a large flat tensor. */
+int clora_mse_weighted_f16(const clora_half* pred, const clora_half* target, const float* weights, float* sample_sums,
+                           clora_half* dpred, int B, size_t n_per_sample, float grad_scale, const float* loss_scale, void* stream);
 int clora_cast_f32_to_f16(const float* x, clora_half* y, size_t n, void* stream);
 int clora_cast_f16_to_f32(const clora_half* x, float* y, size_t n, void* stream);
 
