@@ -102,6 +102,21 @@ class LoraFoldJob(C.Structure):
                 ("rows", C.c_int), ("K", C.c_int), ("nmem", C.c_int), ("m", LoraFoldMember * LORA_FOLD_MAX_MEMBERS)]
 
 
+class ControlMixMember(C.Structure):
+    """mirror of clora_control_mix_member_t"""
+    _fields_ = [("T", C.c_void_p), ("ldt", C.c_int), ("toff", C.c_int), ("U", C.c_void_p), ("ldu", C.c_int), ("r", C.c_int),
+                ("scale", C.c_float)]
+
+
+CONTROL_MIX_MAX_MEMBERS = 8    # CLORA_CONTROL_MIX_MAX_MEMBERS
+
+
+class ControlMixJob(C.Structure):
+    """mirror of clora_control_mix_job_t"""
+    _fields_ = [("Y", C.c_void_p), ("ldy", C.c_int), ("M", C.c_int), ("N", C.c_int), ("rows_t", C.c_int), ("nmem", C.c_int),
+                ("m", ControlMixMember * CONTROL_MIX_MAX_MEMBERS)]
+
+
 class LoraWgradJob(C.Structure):
     """mirror of clora_lora_wgrad_job_t"""
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("T", C.c_void_p), ("ldt", C.c_int), ("toff", C.c_int), ("G", C.c_void_p),
@@ -171,6 +186,7 @@ _PROTOS = {
     "clora_lora_up_f16": [_P, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _I, _I, _F, _P],
     "clora_lora_up_multi_f16": [C.POINTER(LoraUpJob), _I, _P],
     "clora_lora_fold_f16": [_P, _I, _P],
+    "clora_control_mix_q_f16": [C.POINTER(ControlMixJob), _P],
     "clora_lora_wgrad_f16": [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _Z, _P],
     "clora_comm_unique_id": [_P],
     "clora_comm_init": [_P, _I, _I],

@@ -792,6 +792,27 @@ def lora_fold_multi(jobs, device=None):
     return table
 
 
+def control_mix_q(y, n_cols, members, rows_t):
+    """y[:, :n_cols] += sum_i scale_i * T_i[m % rows_t, toff_i : toff_i + r_i] . U_i^T in place, one rounding (include/clora.h
+    clora_control_mix_q_f16): y fp16 [M, ldy] is a site's projection output with the q block first;
+    members = [(T fp32 [rows_t, >= toff + r], toff, U fp32 [n_cols, r], scale), ...].  What the library cannot see (dtypes, the
+    buffers' extents) is checked here; its own contract (sizes, ranks, member count) is the library's to refuse."""
+    if y.dim() != 2 or y.stride(1) != 1 or n_cols > y.shape[1]:
+        raise capi.CloraError(f"control_mix_q: output {tuple(y.shape)} with strides {y.stride()} has no q block of {n_cols} columns")
+    if len(members) > capi.CONTROL_MIX_MAX_MEMBERS:
+        raise capi.CloraError(f"a control mix job takes at most {capi.CONTROL_MIX_MAX_MEMBERS} members, got {len(members)}")
+    job = capi.ControlMixJob(ptr(y, f16), y.stride(0), y.shape[0], int(n_cols), int(rows_t), len(members))
+    for i, (T, toff, U, scale) in enumerate(members):
+        r = U.shape[1]
+        if T.dim() != 2 or U.dim() != 2 or T.stride(1) != 1 or U.stride(1) != 1 or T.shape[0] != rows_t or toff < 0 or \
+                toff + r > T.shape[1] or U.shape[0] != n_cols:
+            raise capi.CloraError(f"control_mix_q: member {i} has T {tuple(T.shape)} (offset {toff}) and U {tuple(U.shape)} for "
+                                  f"{rows_t} control rows and {n_cols} columns")
+        job.m[i] = capi.ControlMixMember(ptr(T, f32), T.stride(0), int(toff), ptr(U, f32), U.stride(0), r, float(scale))
+    _call("clora_control_mix_q_f16", C.byref(job), nbytes=4.0 * y.shape[0] * n_cols)
+    return y
+
+
 def lora_down_multi(jobs):
     """several adapter down-projections (possibly over different inputs) in one launch"""
     for i in range(0, len(jobs), capi.LORA_MAX_JOBS):

@@ -13,7 +13,9 @@ Per attention site the reference launches ~25-30 micro-kernels for the adapters 
 score matrix; here a site is: (control add) -> one fused q|k|v GEMM with the rank-r updates in its epilogue
 -> flash attention -> one out-projection GEMM (+ adapter + bias + residual).  Quirks C1-C9 of SURVEY.md
 Appendix C are kept.  ``post_add=True`` and ``pre_loras`` / ``post_loras`` chains run the
-same kernels unfused in the reference's exact order (`_generic_call`).
+same kernels unfused in the reference's exact order (`_generic_call`); frozen chained members -- plain LoRAs, and with a second
+ControlLoRA (canny + pose, `mix_control_loras`) version-1 control processors -- can instead be folded into the frozen weights
+(`fold_sites`), the control members' guide-only share being one more launch on the q block (`_control_mix`).
 """
 from __future__ import annotations
 
@@ -268,9 +270,25 @@ class LoRACrossAttnProcessor(nn.Module):
         if len(members) > K.capi.LORA_FOLD_MAX_MEMBERS:
             return f"more than {K.capi.LORA_FOLD_MAX_MEMBERS} chained adapters"
         kv_in = self.cross_attention_dim or self.hidden_size
+        control_ok = getattr(self, "fold_control_members", False)
         for m in members:
-            if type(m) is not LoRACrossAttnProcessor:
+            control = control_ok and type(m) is ControlLoRACrossAttnProcessor
+            if type(m) is not LoRACrossAttnProcessor and not control:
                 return f"a member is a {type(m).__name__}, not a plain LoRACrossAttnProcessor"
+            if control:
+                # a frozen v1 control member: its adapters fold like a plain member's, its control share is `_control_mix`
+                if getattr(self, "version", 0) != 1:
+                    return "a member is a control processor and the main processor is not version 1"
+                if m.concat_hidden:
+                    return "a control member is concat_hidden"
+                if m._chain_members():
+                    return "a control member has a chain of its own"
+                if m.to_q_lora.down.weight.shape[0] > 16:
+                    return "a control member's q adapter has a rank above 16"
+                if m.control_states is None:
+                    return "a control member has no control states injected"
+                if torch.is_grad_enabled():
+                    return "a member is a control processor and autograd is on"
             if m.post_add:
                 return "a member is post_add"
             if m.hidden_size != self.hidden_size or (m.cross_attention_dim or m.hidden_size) != kv_in:
@@ -279,7 +297,63 @@ class LoRACrossAttnProcessor(nn.Module):
                 return "a member is not held in fp32"
         if torch.is_grad_enabled() and any(q.requires_grad for m in members for q in m.parameters()):
             return "a member is trainable and autograd is on"
+        ctl = [m for m in members if type(m) is ControlLoRACrossAttnProcessor]
+        if len(ctl) > K.capi.CONTROL_MIX_MAX_MEMBERS or sum(m.to_q_lora.down.weight.shape[0] for m in ctl) > 32:
+            return f"more than {K.capi.CONTROL_MIX_MAX_MEMBERS} control members, or their q adapters' ranks sum to more than 32"
         return None
+
+    def _control_mix(self, B, N, dtype, scale):
+        """-> (members of kernels.control_mix_q, rows_t) for the frozen control members of this site's chain, or None without any.
+        Only reached on the folded path (`_fold_blocker` is None).  A member's q adapter reads h + c_m, c_m = s U_cm D_cm ctrl_m
+        (reference models.py:232-243): the share over h is in the folded weights, the rest is s^2 U_qm t_m with
+        t_m = (D_qm U_cm)(D_cm ctrl_m) [Mc, r] -- the member's rank-space control share at scale 1, which depends on its guide
+        and weights alone.  Built once per (control states, parameters, chain, scale): keyed on storage / version like the fold."""
+        ctl = [m for m in self._chain_members() if type(m) is ControlLoRACrossAttnProcessor]
+        if not ctl:
+            return None
+        scale = float(scale)
+        probe = torch.empty((B, N, 0), dtype=dtype)
+        ctrls, srcs, key = [], [], [scale, B, N]
+        for m in ctl:
+            ctrl = m._control_tokens(probe)                 # [b, N, Cc]; raises for a control batch that is neither 1 nor B
+            if ctrl.shape[1] != N:
+                raise ValueError(f"a control member's map has {ctrl.shape[1]} tokens, the site has {N}")
+            tq = getattr(m, "_control_T", None)
+            if not (tq is not None and getattr(m, "_control_term_scale", None) == 1.0 and m.to_q_lora.down.weight.shape[0] == 4):
+                tq = None                                   # (left by the member model's forward: the very t_m, columns 0..3)
+            src = tq if tq is not None else m.control_states     # (as injected: `ctrl` may be a cast made for this call)
+            ws = (m.to_q_lora.up.weight,) if tq is not None else \
+                (m.to_q_lora.up.weight, m.to_q_lora.down.weight, m.to_control.down.weight, m.to_control.up.weight)
+            key.append((id(m), id(src), src.data_ptr(), src._version, tuple(src.shape), tuple((w.data_ptr(), w._version) for w in ws)))
+            ctrls.append(ctrl)
+            srcs.append(tq)
+        key = tuple(key)
+        st = self.__dict__.get("_mix")
+        if st is not None and st["key"] == key:
+            return st["members"], st["rows_t"]
+        if K.capi.lib().require_device and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a chained adapter, its scale or the frozen weights changed inside a graph capture: run one forward "
+                               "(or ControlLoRA.fold_now) before capturing, the fold is not part of the captured step")
+        rows_t = max(c.shape[0] for c in ctrls) * N
+        members = []
+        with torch.no_grad():
+            for m, ctrl, tq in zip(ctl, ctrls, srcs):
+                r = m.to_q_lora.down.weight.shape[0]
+                if tq is None:
+                    c2 = _flat2(ctrl)
+                    tri = (m.to_control.down.weight.detach(), m.to_control.up.weight.detach(), m.to_q_lora.down.weight.detach())
+                    if ops.RANK_CONTROL and ops.rank_control_ok([tri]):
+                        tq = ops.control_terms_rank(c2, [tri], 1.0)[0]
+                    else:                                   # other ranks: the materialised term once, then its down-projection
+                        c = ops.control_term(c2, tri[0], tri[1], 1.0, c2.shape[0])
+                        tq = K.lora_down(c, tri[2], torch.empty((c2.shape[0], r), dtype=f32, device=c.device), 0, c2.shape[0],
+                                         tri[2].shape[1])
+                if tq.shape[0] != rows_t:                   # a control batch of 1 beside one of B: tile it once
+                    tq = tq.repeat(rows_t // tq.shape[0], 1)
+                members.append((tq, 0, m.to_q_lora.up.weight.detach(), scale * scale))
+        # (the sources are kept referenced: a new tensor can then never show up at a keyed address)
+        self.__dict__["_mix"] = dict(key=key, members=members, rows_t=rows_t, keep=(ctrls, srcs, [m.control_states for m in ctl]))
+        return members, rows_t
 
     def _site_packs(self, attn, scale):
         """-> (q|k|v packs, out pack, fold generation) of the fused path: the module's own (generation None), or the folded ones
@@ -343,6 +417,8 @@ class LoRACrossAttnProcessor(nn.Module):
 
     def _attend(self, attn, h2, q_in, e2, B, N, Nk, scale, out_in_fn, residual, own_out_always, t_pre=None):
         packs, out_pack, fold_gen = self._site_packs(attn, scale)
+        # frozen control members of a folded chain: their control share joins the q block right after the projection
+        mix = self._control_mix(B, N, h2.dtype, scale) if fold_gen is not None else None
         # t_pre: the control term's share of the q adapter's down-projection -- in rank space (ops.control_terms_rank: q_in is
         # the hidden states alone then), or, with the materialised term (q_in = (h, c)), c . D_q^T evaluated for the whole level
         # in one launch (ops.control_q_parts; only meaningful with that very c)
@@ -350,6 +426,8 @@ class LoRACrossAttnProcessor(nn.Module):
             t_pre = getattr(self, "_control_T", None)
         if attn.is_cross:
             q = ops.lora_proj(h2, packs[0], [self._seg("to_q_lora", q_in, scale)], t_pre=t_pre[:, :4] if t_pre is not None else None)
+            if mix is not None:
+                K.control_mix_q(q, h2.shape[1], *mix)
             grp = _TEXT_GROUPS.get(id(attn)) if (_TEXT_GROUPS is not None and torch.is_grad_enabled()) else None
             if grp is not None and grp[2] is self and grp[3] == float(scale) and grp[0].e2.data_ptr() == e2.data_ptr():
                 # k | v of this site were evaluated with every other site of its width at the head of the UNet forward
@@ -370,6 +448,8 @@ class LoRACrossAttnProcessor(nn.Module):
             qkv = ops.lora_proj(h2, packs[0], [self._seg("to_q_lora", q_in, scale),
                                                self._seg("to_k_lora", h2, scale, self.key_states_skipped),
                                                self._seg("to_v_lora", h2, scale, self.value_states_skipped)], t_pre=t_pre)
+            if mix is not None:
+                K.control_mix_q(qkv, h2.shape[1], *mix)
             a = attn.attend(qkv, None, B, N, N)
         a = out_in_fn(a)
         out_seg = self._seg("to_out_lora", a, scale, (not own_out_always) and self.output_states_skipped)
@@ -399,6 +479,8 @@ def fold_sites(pairs, scale=1.0):
     flags, the main processor's version and `scale`: an in-place update, load_state_dict, another scale or an edited chain
     refolds.  Scaling quirks as in `_generic_call`: a member's value adapter is scaled by `scale` only under a version-0 main
     processor, else by 1.0 (C3); a member's key / value / out adapter is left out when that member's own skip flag is set.
+    A frozen version-1 control member (`fold_control_members`) hands over its q / k / v / out adapters exactly as a plain member
+    does; what its control map adds to q is not a weight and is the site's `_control_mix`.
     -> number of sites that were (re)folded."""
     scale = float(scale)
     jobs, fresh = [], []
@@ -444,6 +526,7 @@ def fold_sites(pairs, scale=1.0):
 
 class _ControlMixin:
     fold_chain = False        # opt-in: frozen plain LoRAs chained onto this site ride in its frozen weights (fold_sites)
+    fold_control_members = False   # opt-in beside it: frozen v1 control members fold too (LoRACrossAttnProcessor._control_mix)
 
     def inject_pre_lora(self, lora_layer):
         self.pre_loras.append(lora_layer)
@@ -782,12 +865,16 @@ class ControlLoRA(nn.Module):
     def _named_processors(self):
         return [(f"lora_layers.{i}.{j}", p) for i, level in enumerate(self.lora_layers) for j, p in enumerate(level)]
 
-    def fold_chains(self, enabled: bool = True):
-        """opt in (or out): every site whose chain is eligible (`fold_report`) runs the fused path on W + s U D"""
+    def fold_chains(self, enabled: bool = True, control_members: bool = False):
+        """opt in (or out): every site whose chain is eligible (`fold_report`) runs the fused path on W + s U D;
+        control_members: frozen version-1 ControlLoRA processors chained on (models.mix_control_loras) are eligible too"""
         for _, p in self._named_processors():
             p.fold_chain = bool(enabled)
+            p.fold_control_members = bool(enabled and control_members)
             if not enabled:
                 p.__dict__.pop("_fold", None)
+            if not p.fold_control_members:
+                p.__dict__.pop("_mix", None)
         return self
 
     def fold_report(self) -> dict:
@@ -795,7 +882,9 @@ class ControlLoRA(nn.Module):
         rep = {}
         for name, p in self._named_processors():
             why = p._fold_blocker()
-            rep[name] = dict(folded=why is None, reason=why, members=len(p._chain_members()))
+            chain = p._chain_members()
+            rep[name] = dict(folded=why is None, reason=why, members=len(chain),
+                             control_members=sum(isinstance(m, _ControlMixin) for m in chain))
         return rep
 
     def fold_now(self, unet, scale: float = 1.0) -> int:
@@ -909,5 +998,40 @@ def mix_lora_into_control_lora(unet, control_lora, lora_procs, pre=True, post=Fa
         if post:
             proc.inject_post_lora(member)
     control_lora.fold_chains(bool(fold))
+    unet.set_attn_processor(sites)
+    return sites
+
+
+def mix_control_loras(unet, main, members, pre=True, post=False, fold=True) -> dict:
+    """Chain further ControlLoRA models onto `main` site by site, so that several guides (canny + pose) steer one image: every
+    member model's processors are mapped onto the UNet like the main model's and injected name by name (reference
+    models.py:232-243, 366-372, 412-418: a chained member that is itself a control processor adds its own control term), and the
+    main model's processors are installed.  fold: freeze the members and let every eligible site run fused
+    (ControlLoRA.fold_chains(True, control_members=True); `fold_report()` tells which).  Mixed control versions are refused: the
+    reference's isinstance checks would silently drop such a member's control.  -> the installed name -> processor mapping."""
+    members = list(members)
+    version = int(main.config["lora_control_version"])
+    for i, mm in enumerate(members):
+        v = int(mm.config["lora_control_version"])
+        if (v == 2) != (version == 2):
+            raise ValueError(f"member {i} is a version-{v} control model, the main model is version {version}: the reference ignores "
+                             "the control of a member of another version")
+    sites = map_processors_to_unet(unet, main)
+    mapped = []
+    for i, mm in enumerate(members):
+        msites = map_processors_to_unet(unet, mm)
+        lacking = sorted(set(sites) - set(msites))
+        if lacking:
+            raise ValueError(f"member {i} has no processor for the sites {lacking[:4]}")
+        mapped.append(msites)
+    for mm, msites in zip(members, mapped):
+        if fold:
+            mm.requires_grad_(False)
+        for name, proc in sites.items():
+            if pre:
+                proc.inject_pre_lora(msites[name])
+            if post:
+                proc.inject_post_lora(msites[name])
+    main.fold_chains(bool(fold), control_members=bool(fold))
     unet.set_attn_processor(sites)
     return sites

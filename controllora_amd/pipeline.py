@@ -13,6 +13,8 @@ from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guidance_scale=9.0, latents=None,
                 generator=None, sampler="ddim", graph=None, cache_text_kv=True, callback=None, size=None):
     """guide [Bc,3,H,W] (control batch 1 broadcasts over the CFG batch, quirk C6); cond/uncond [B,77,768].
+    control_lora / guide may be equal-length lists: the main model (whose processors sit on the UNet) first, then the models
+    chained onto it with models.mix_control_loras, each with the guide it reads.
     sampler: "ddim" (BASELINE inference config) or "dpm" (DPM-Solver++(2M), what the reference apps select).
 
     What is invariant over the scheduler loop is evaluated ONCE: the hint encoder and the 32 control terms (reference
@@ -27,6 +29,19 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
     from . import models
     B = cond_emb.shape[0]
     dev = cond_emb.device
+    # several control models steering one image (models.mix_control_loras): equal-length lists, the main model first
+    many = isinstance(control_lora, (list, tuple))
+    if many or isinstance(guide, (list, tuple)):
+        control_loras = list(control_lora) if many else [control_lora]
+        guides = list(guide) if isinstance(guide, (list, tuple)) else [guide]
+        if len(control_loras) != len(guides) or not control_loras or any(c is None for c in control_loras) or \
+                any(g is None for g in guides):
+            raise ValueError(f"{len(control_loras)} control models and {len(guides)} guide images: every control model needs a guide of its own")
+        if len({tuple(g.shape[2:]) for g in guides}) != 1:
+            raise ValueError(f"the guides must share one size, got {[tuple(g.shape[2:]) for g in guides]}")
+        control_lora, guide = control_loras[0], guides[0]
+    else:
+        control_loras, guides = [control_lora], [guide]
     if guide is not None:
         H, W = guide.shape[2] // 8, guide.shape[3] // 8
     elif control_lora is not None:
@@ -48,11 +63,17 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
         # validated ONCE here (the per-site check in models._control_tokens is bypassed by precomputed control terms): a
         # control batch of 1 broadcasts; one guide per image is tiled the way the CFG batch is (uncond..., cond...), which
         # makes the batches equal; anything else has no defined pairing (reference quirk C6) and is rejected
-        if guide.shape[0] == B and B > 1:
-            guide = torch.cat([guide, guide], 0)
-        elif guide.shape[0] not in (1, 2 * B):
-            raise ValueError(f"guide batch {guide.shape[0]}: expected 1 (broadcast) or one guide per image ({B})")
-        control_lora(guide)
+        tiled = []
+        for gd in guides:
+            if gd.shape[0] == B and B > 1:
+                gd = torch.cat([gd, gd], 0)
+            elif gd.shape[0] not in (1, 2 * B):
+                raise ValueError(f"guide batch {gd.shape[0]}: expected 1 (broadcast) or one guide per image ({B})")
+            tiled.append(gd)
+        # every model's hint encoder once; the chained members first, so that the main model's forward already sees a chain that
+        # folds and evaluates its sites' control terms for the fused path
+        for model, gd in reversed(list(zip(control_loras, tiled))):
+            model(gd)
     ehs = torch.cat([uncond_emb, cond_emb], 0).half().contiguous()
     if graph is None:
         # capture costs one extra warm-up forward + the capture itself: only worth it for real sampling runs
@@ -96,16 +117,29 @@ class ControlLoRAPipeline:
 
         pipe = ControlLoRAPipeline.from_pretrained("random:sd15", "path/to/control_lora")
         images = pipe("a red circle", guide, num_samples=4, ddim_steps=50, scale=9.0, seed=1)   # uint8 [N, H, W, 3]
+
+    Several control models (canny + pose): `from_pretrained(base, [main, member, ...])` chains the members onto the main model
+    (models.mix_control_loras; fold=False keeps the unfused path) and `pipe(prompt, guide=[g_main, g_member, ...])`.
     """
 
     def __init__(self, unet, control_lora, vae, text_encoder, tokenizer):
         self.unet, self.control_lora, self.vae, self.text_encoder, self.tokenizer = unet, control_lora, vae, text_encoder, tokenizer
 
     @classmethod
-    def from_pretrained(cls, base: str, control_lora, device="cuda"):
+    def from_pretrained(cls, base: str, control_lora, device="cuda", fold=True):
         from . import loading, models, text
         dev = torch.device(device)
         unet = loading.load_unet(base, dev)
+        if isinstance(control_lora, (list, tuple)):    # [main, member, ...]: several guides steer one image
+            loaded = [(models.ControlLoRA.from_pretrained(c) if isinstance(c, str) else c).to(dev) for c in control_lora]
+            if not loaded:
+                raise ValueError("an empty list of control models")
+            if len(loaded) == 1:
+                unet.set_attn_processor(models.map_processors_to_unet(unet, loaded[0]))
+            else:
+                models.mix_control_loras(unet, loaded[0], loaded[1:], pre=True, post=False, fold=fold)
+            return cls(unet, loaded, loading.load_vae(base, dev), text.load_text_encoder(base, dev, small=base.endswith("small")),
+                       text.load_tokenizer(base))
         if isinstance(control_lora, str):
             control_lora = models.ControlLoRA.from_pretrained(control_lora)
         if control_lora is not None:                   # None: the frozen base model alone, plain text-to-image
@@ -124,7 +158,8 @@ class ControlLoRAPipeline:
                  output_type="uint8", sampler="ddim", height=None, width=None):
         """guide: float tensor [1, 3, H, W] (broadcast over the samples) or [num_samples, 3, H, W] (one guide per image), in
         [-1, 1]; H, W multiples of 64, square or not -- every size the reference apps' image_resolution slider gives (256 ... 768):
-        the UNet's and the VAE's attention are flash kernels that take any number of tokens.
+        the UNet's and the VAE's attention are flash kernels that take any number of tokens.  A pipeline built from a list of control
+        models ([main, member, ...]) takes a list of guides, one per model in that order, all of one size.
         A pipeline without a control model takes no guide: `height` / `width` (multiples of 64, default 512) size the image."""
         if guide is None:
             if self.control_lora is not None:
@@ -138,7 +173,13 @@ class ControlLoRAPipeline:
             gen.manual_seed(int(seed))
         cond = self.encode_prompt([prompt + (", " + a_prompt if a_prompt else "")] * num_samples)
         uncond = self.encode_prompt([n_prompt] * num_samples)
-        lat = ddim_sample(self.unet, self.control_lora, None if guide is None else guide.to(dev).half(), cond, uncond,
+        if isinstance(guide, (list, tuple)):
+            guide = [g.to(dev).half() for g in guide]
+        elif guide is not None:
+            guide = guide.to(dev).half()
+            if isinstance(self.control_lora, (list, tuple)):
+                guide = [guide]                        # (a list of one model takes a bare guide too)
+        lat = ddim_sample(self.unet, self.control_lora, guide, cond, uncond,
                           steps=ddim_steps, guidance_scale=scale, generator=gen, sampler=sampler,
                           size=None if guide is not None else (height, width))
         img = self.vae.decode(lat.half() / self.vae.scaling_factor).sample.float().clamp(-1, 1)

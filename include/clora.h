@@ -559,6 +559,29 @@ typedef struct {
     clora_lora_fold_member_t m[CLORA_LORA_FOLD_MAX_MEMBERS];
 } clora_lora_fold_job_t;
 int clora_lora_fold_f16(const clora_lora_fold_job_t* jobs, int njobs, void* stream);
+/* The part of a frozen ControlLoRA member chained onto a v1 site that is not a weight (reference models.py:232-243: a member's q
+ * adapter reads hidden_states + its own control term).  Its share over the hidden states is folded (clora_lora_fold_f16); the rest,
+ * scale^2 * up_q . t with t = (down_q . up_c)(down_c . control) in rank space (clora_rank_compose_f32), depends on the guide alone
+ * and is added to the q column block of the site's projection output, in place:
+ *   Y[m, n] = fp16( float(Y[m, n]) + sum_i scale_i * sum_j T_i[m % rows_t, toff_i + j] * U_i[n, j] ),  i < nmem, j < r_i
+ * Y: [M, N] with row pitch ldy (the q block of a [M, 3N] q|k|v output, or a [M, N] q output), 16-byte aligned; T_i: fp32 [rows_t, ..]
+ * with row pitch ldt; U_i: fp32 [N, r_i] with row pitch ldu.  rows_t is the control map's row count: the tokens of one image for a
+ * control batch of 1 (the map is tiled over the batch), or M.  N % 8 == 0, ldy % 8 == 0, ldy >= N, 1 <= r_i <= 16, sum r_i <= 32,
+ * M % rows_t == 0, 1 <= nmem <= CLORA_CONTROL_MIX_MAX_MEMBERS: a job that breaks this returns CLORA_ERR_ARG and launches nothing.
+ * `job` is HOST memory, read at the call.  The sum is formed in fp32, members in order, ranks in order, and rounded once together
+ * with Y.  Deterministic: no atomics, every element is produced by one thread. */
+#define CLORA_CONTROL_MIX_MAX_MEMBERS 8
+typedef struct {
+    const float* T; int ldt, toff;
+    const float* U; int ldu, r;
+    float scale;
+} clora_control_mix_member_t;
+typedef struct {
+    clora_half* Y;
+    int ldy, M, N, rows_t, nmem;
+    clora_control_mix_member_t m[CLORA_CONTROL_MIX_MAX_MEMBERS];
+} clora_control_mix_job_t;
+int clora_control_mix_q_f16(const clora_control_mix_job_t* job, void* stream);
 /* G[n*gs_n + j*gs_j] += scale * sum_m A[m, n] * T[m, toff+j]  (adapter weight gradients; two-stage
  * deterministic reduction through `workspace` of clora_lora_wgrad_workspace_bytes(M, N, R) bytes, no atomics). */
 size_t clora_lora_wgrad_workspace_bytes(int M, int N, int R);
