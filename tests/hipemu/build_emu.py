@@ -24,10 +24,38 @@ def _host_isa_flags():
     return ["-mf16c", "-mavx2", "-mfma"] if all(f" {f}" in flags for f in ("f16c", "avx2", "fma")) else []
 
 
+def _includes(path: str) -> set:
+    """base names of the project headers a source file names in `#include "..."` lines (a textual scan: conditional includes count)"""
+    import re
+    return {os.path.basename(m) for m in re.findall(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', open(path).read(), re.M)}
+
+
+def units_including(src_dir: str, file_name: str) -> set:
+    """base names of the translation units of ``src_dir`` that must be recompiled when ``file_name`` changes: the file itself when it
+    is a ``.hip``, else every ``.hip`` whose text includes that header directly or through another header of the directory"""
+    if file_name.endswith(".hip"):
+        return {file_name}
+    hit = set()
+    for src in glob.glob(os.path.join(src_dir, "*.hip")):
+        seen, todo = set(), [src]
+        while todo:
+            for inc in _includes(todo.pop()):
+                if inc not in seen:
+                    seen.add(inc)
+                    if os.path.exists(os.path.join(src_dir, inc)):
+                        todo.append(os.path.join(src_dir, inc))
+        if file_name in seen:
+            hit.add(os.path.basename(src))
+    return hit
+
+
 def build_mutant(out_dir: str, file_name: str, edits) -> str:
     """The emulator library with some source lines of ``csrc/<file_name>`` replaced (``edits`` = [(old, new)], each ``old`` must
     occur exactly once): used by the
-    tests that prove the emulator's pessimistic LDS-DMA model catches a weakened ``s_waitcnt`` (tests/test_emu_async_model.py)."""
+    tests that prove the emulator's pessimistic LDS-DMA model catches a weakened ``s_waitcnt`` (tests/test_emu_async_model.py) and that
+    the kernel cases fail on a subtly wrong kernel (tests/test_attention_mutants_emu.py, tests/test_kernel_mutants_emu.py).
+    ``file_name`` may be a header of ``csrc``: every translation unit that includes it (units_including) is recompiled then, and an
+    edit that no translation unit would see is an error."""
     import shutil
     src_dir = os.path.join(out_dir, "controllora_amd", "csrc")      # same depth as the real tree: the sources include
     shutil.copytree(CSRC, src_dir)                                  # "../../include/clora.h"
@@ -39,10 +67,13 @@ def build_mutant(out_dir: str, file_name: str, edits) -> str:
             raise ValueError(f"{file_name}: mutation anchor {old!r} occurs {text.count(old)} times")
         text = text.replace(old, new)
     open(path, "w").write(text)
+    rebuild = units_including(src_dir, file_name)
+    if not rebuild:
+        raise ValueError(f"{file_name}: no translation unit includes it, the mutation would change nothing")
     objs = []
     for src in sorted(glob.glob(os.path.join(src_dir, "*.hip"))):
         base = os.path.basename(src).rsplit(".", 1)[0] + ".emu.o"
-        if os.path.basename(src) != file_name and os.path.exists(os.path.join(OUT_DIR, base)):
+        if os.path.basename(src) not in rebuild and os.path.exists(os.path.join(OUT_DIR, base)):
             objs.append(os.path.join(OUT_DIR, base))          # untouched translation units: reuse the regular build
             continue
         obj = os.path.join(out_dir, base)

@@ -737,16 +737,32 @@ def case_layernorm_rows(dev, M, C, seed=25):
         assert rel(a, b_) < 1e-5, rel(a, b_)
 
 
+EW_CAP = 4096 * 256        # work items (16-byte vectors, or elements for the casts) one trip of a capped elementwise grid covers (ew_grid)
+
+
+def check_past_cap(out, ref, first, lim, what):
+    """rel-L2 limit + no_outliers on the whole tensor and, when the launch needs more than one trip of its grid-stride loop, again on
+    the part from flat index / row `first` on: a defect confined to the later trips is diluted by the first million correct vectors"""
+    out, ref = out.reshape(-1, out.shape[-1]) if out.dim() > 1 else out, ref.reshape(-1, ref.shape[-1]) if ref.dim() > 1 else ref
+    parts = [("", out, ref)] + ([(" past the first trip", out[first:], ref[first:])] if first < out.shape[0] else [])
+    for tag, o, r_ in parts:
+        e = rel(o, r_)
+        assert e < lim, (what + tag, e)
+        no_outliers(o, r_, what + tag)
+
+
 def case_geglu(dev, M, Fdim, seed=6):
+    """M * Fdim / 8 > EW_CAP: the rows from EW_CAP // (Fdim / 8) + 1 on belong to later trips of the grid-stride loop alone"""
     g = torch.Generator().manual_seed(seed)
     h = rnd((M, 2 * Fdim), dev, g)
     h32 = h.float().clone().requires_grad_(True)
     a, gg = h32.chunk(2, -1)
     y = a * F.gelu(gg)
-    assert rel(K.geglu_fwd(h), y.detach()) < 6e-4
+    later = EW_CAP // (Fdim // 8) + 1
+    check_past_cap(K.geglu_fwd(h), y.detach(), later, 6e-4, "geglu_fwd")
     dy = rnd((M, Fdim), dev, g)
     y.backward(dy.float())
-    assert rel(K.geglu_bwd(h, dy), h32.grad) < 8e-4
+    check_past_cap(K.geglu_bwd(h, dy), h32.grad, later, 8e-4, "geglu_bwd")
 
 
 def case_lora(dev, M, Kd, N, R, x_rows=0, seed=7):
@@ -768,24 +784,51 @@ def case_lora(dev, M, Kd, N, R, x_rows=0, seed=7):
         assert rel(T2[:, 4:], Tref + X2.float() @ D.T) < 1e-5
     T[:, 4:] = Tref
     base = rnd((M, N), dev, g)
-    y = K.lora_up(base, T, 4, U, M, N, 0.6)
+    nan_out = lambda: torch.full((M, N), float("nan"), dtype=f16, device=dev)      # an element the launch skips stays NaN
+    y = K.lora_up(base, T, 4, U, M, N, 0.6, out=nan_out())
     ref = base.float() + (0.6 * (Tref @ U.T).half().float()).half().float()
     assert rel(y, ref) < 6e-4
-    y0 = K.lora_up(None, T, 4, U, M, N, 1.0)
+    later = EW_CAP // (N // 8) + 1                # rows the capped grid of lora_up reaches on a later trip only (M * N / 8 > EW_CAP)
+    if later < M:
+        assert rel(y[later:], ref[later:]) < 6e-4
+    y0 = K.lora_up(None, T, 4, U, M, N, 1.0, out=nan_out())
     assert rel(y0, Tref @ U.T) < 6e-4
+    if later < M:
+        assert rel(y0[later:], (Tref @ U.T)[later:]) < 6e-4
+    # the weight gradients are ADDED to what the caller's buffer holds (the optimizer's flat gradient buffer): start from a fill
     A = rnd((rows, N), dev, g)
-    G1 = torch.zeros((N, R), dtype=f32, device=dev)
+    fill = 0.75
+    G1 = torch.full((N, R), fill, dtype=f32, device=dev)
     K.lora_wgrad(A, T, 4, G1, R, 1, M, N, R, scale=0.5, a_rows=x_rows)
     Af = A.float().repeat(M // rows, 1) if x_rows else A.float()
-    assert rel(G1, 0.5 * Af.T @ Tref) < 1e-4
-    G2 = torch.zeros((R, N), dtype=f32, device=dev)
+    assert rel(G1 - fill, 0.5 * Af.T @ Tref) < 1e-4
+    G2 = torch.full((R, N), fill, dtype=f32, device=dev)
     K.lora_wgrad(A, T, 4, G2, 1, N, M, N, R, scale=1.0, a_rows=x_rows)
-    assert rel(G2, (Af.T @ Tref).T) < 1e-4
+    assert rel(G2 - fill, (Af.T @ Tref).T) < 1e-4
     if R <= 16:                                   # reduction over fp16(A + A2)
         A2 = rnd((M, N), dev, g)
-        G3 = torch.zeros((N, R), dtype=f32, device=dev)
+        G3 = torch.full((N, R), fill, dtype=f32, device=dev)
         K.lora_wgrad_multi([K.wgrad_job(A, T, 4, G3, R, 1, M, N, R, a_rows=x_rows, A2=A2)], dev)
-        assert rel(G3, (Af + A2.float()).half().float().T @ Tref) < 1e-4
+        assert rel(G3 - fill, (Af + A2.float()).half().float().T @ Tref) < 1e-4
+
+
+def case_lora_wgrad_multi(dev, shapes=((2113, 40), (70, 520), (300, 64)), R=4, seed=71):
+    """ONE clora_lora_wgrad_multi_f16 launch whose jobs differ in M and N (grid = the largest job's: the others' surplus blocks exit;
+    34 / 2 / 5 row blocks, one job with a second column block): every job's gradient equals its single-job launch bit for bit (same
+    slabs, same fold order) and agrees with fp32 torch (1e-4, case_lora's limit); the buffers start from a fill."""
+    g = torch.Generator().manual_seed(seed)
+    fill = -0.5
+    As = [rnd((M, N), dev, g) for M, N in shapes]
+    Ts = [rnd((M, R), dev, g, 0.5, f32) for M, _ in shapes]
+    single = [torch.full((N, R), fill, dtype=f32, device=dev) for _, N in shapes]
+    multi = [s_.clone() for s_ in single]
+    for A, T, G, (M, N) in zip(As, Ts, single, shapes):
+        K.lora_wgrad_multi([K.wgrad_job(A, T, 0, G, R, 1, M, N, R, scale=0.5)], dev)
+    K.lora_wgrad_multi([K.wgrad_job(A, T, 0, G, R, 1, M, N, R, scale=0.5) for A, T, G, (M, N) in zip(As, Ts, multi, shapes)], dev)
+    for A, T, Gs, Gm, shape in zip(As, Ts, single, multi, shapes):
+        assert torch.equal(Gs, Gm), (shape, "multi-job launch differs from the single-job one", rel(Gm, Gs))
+        e = rel(Gm - fill, 0.5 * A.float().T @ T)
+        assert e < 1e-4, (shape, e)
 
 
 def case_elementwise(dev, seed=8):
@@ -813,6 +856,91 @@ def case_elementwise(dev, seed=8):
         assert float((out.float() - ref).abs().max()) <= 1e-3            # one fp16 rounding of a value in [-1, 1]
         frac_equal = float((out == ref.to(f16)).float().mean())
         assert frac_equal > 0.99, frac_equal
+
+
+def fp16_rounding_margin(ref):
+    """limit for an fp16 result checked against an fp32 reference where the project states none yet: four times the rel-L2 distance
+    of the reference's own fp16 rounding from it (the error of a perfect kernel)"""
+    return 4.0 * rel(ref.half(), ref)
+
+
+def case_elementwise_past_cap(dev, n=(EW_CAP + 300) * 8, seed=81):
+    """The elementwise kernels where their grid is capped (ew_grid: 4096 blocks of 256) and the grid-stride loop takes a second trip --
+    what the product does on every activation of the upper UNet levels.  add and the two casts are one rounding of exact inputs: bit
+    equality.  silu / silu_bwd keep case_elementwise's limits.  quick_gelu had no reference check: fp32 torch on the same fp16 inputs,
+    limit = fp16_rounding_margin (reference rounding 2.07e-4 -> limit 8.27e-4; measured: emulator 2.07e-4, MI355X 2.07e-4).  Every
+    check is repeated on the elements past the first trip alone (check_past_cap).  The entry points are called on outputs that start
+    as NaN (the wrappers of kernels.py allocate theirs uninitialised, and an allocator may hand back the block that held the right
+    answer a moment ago): an element a launch never writes fails the check whatever memory it landed in."""
+    g = torch.Generator().manual_seed(seed)
+    a, b = rnd((n,), dev, g), rnd((n,), dev, g)
+    first = EW_CAP * 8                                               # 8 halves per vector
+
+    def run(entry, *ins, dtype=f16):
+        y = torch.full((n,), float("nan"), dtype=dtype, device=dev)
+        K._call(entry, *[K.ptr(x, x.dtype) for x in ins], K.ptr(y), n)
+        return y
+
+    y = run("clora_add_f16", a, b)
+    want = (a.float() + b.float()).half()
+    assert torch.equal(y, want), ("add", int((y != want).sum()), int((y[first:] != want[first:]).sum()))
+    check_past_cap(run("clora_silu_f16", a), F.silu(a.float()), first, 5e-4, "silu")
+    a32 = a.float().clone().requires_grad_(True)
+    F.silu(a32).backward(b.float())
+    check_past_cap(run("clora_silu_bwd_f16", a, b), a32.grad, first, 6e-4, "silu_bwd")
+    ref = a.float() * torch.sigmoid(1.702 * a.float())
+    lim = fp16_rounding_margin(ref)
+    out = run("clora_quick_gelu_f16", a)
+    print(f"QUICK_GELU n={n} rel={rel(out, ref):.3e} limit={lim:.3e}")
+    check_past_cap(out, ref, first, lim, "quick_gelu")
+    # the casts walk ELEMENTS: n elements are 8 trips, everything from EW_CAP on is a later one
+    x32 = (a.float() * 1.0009765625 + 1e-5).contiguous()             # not representable in fp16: the cast has to round
+    h = run("clora_cast_f32_to_f16", x32)
+    assert torch.equal(h, x32.half()), ("to_f16", int((h != x32.half()).sum()), int((h[EW_CAP:] != x32.half()[EW_CAP:]).sum()))
+    back = run("clora_cast_f16_to_f32", a, dtype=f32)
+    assert torch.equal(back, a.float()), ("cast_f16_to_f32", int((back != a.float()).sum()))
+    for wrapped, direct in ((K.add(a, b), y), (K.quick_gelu(a), out), (K.to_f16(x32), h)):      # the wrappers launch the same thing
+        assert torch.equal(wrapped, direct)
+
+
+def case_copies_past_cap(dev, shape=(32, 1100), Ca=240, Cb=248, seed=82):
+    """concat_channels / split_channels (clora_copy2d_f16, strided on one side) with more than EW_CAP 16-byte vectors per copy
+    (35200 rows x 30 / 31 vectors): bit equality with torch.cat / slicing"""
+    g = torch.Generator().manual_seed(seed)
+    assert shape[0] * shape[1] * min(Ca, Cb) // 8 > EW_CAP
+    a, c = rnd(shape + (Ca,), dev, g), rnd(shape + (Cb,), dev, g)
+    cat = K.concat_channels(a, c)
+    want = torch.cat([a, c], -1)
+    assert torch.equal(cat, want), ("concat", int((cat != want).any(-1).sum()), "rows differ")
+    sa, sc = K.split_channels(cat, Ca)
+    assert torch.equal(sa, a) and torch.equal(sc, c), ("split", int((sa != a).any(-1).sum()), int((sc != c).any(-1).sum()), "rows differ")
+
+
+def case_pool2x2_sum(dev, B, H, W, C_, seed=83):
+    """clora_pool2x2_sum_f16 (backward of the nearest-neighbour 2x upsampling): dx[b, y, x] = the sum of the 2 x 2 block of dy, fp32
+    torch on the same fp16 inputs.  Only case_conv(ups=True) reached it, through a convolution's dgrad and at 1e-3.  Limit =
+    fp16_rounding_margin (reference rounding 2.12e-4 -> limit 8.47e-4; measured: emulator 2.12e-4, MI355X 2.12e-4), whole tensor and past the
+    first trip of the capped grid (B * H * W * C / 8 > EW_CAP at the large shape)."""
+    g = torch.Generator().manual_seed(seed)
+    dy = rnd((B, 2 * H, 2 * W, C_), dev, g)
+    d32 = dy.float()
+    ref = ((d32[:, 0::2, 0::2] + d32[:, 0::2, 1::2]) + d32[:, 1::2, 0::2]) + d32[:, 1::2, 1::2]
+    out = K.pool2x2_sum(dy.reshape(B, 4 * H * W, C_), B, H, W, C_)
+    lim = fp16_rounding_margin(ref)
+    print(f"POOL2X2 {(B, H, W, C_)} rel={rel(out, ref.reshape(B, H * W, C_)):.3e} limit={lim:.3e}")
+    check_past_cap(out.reshape(-1), ref.reshape(-1), EW_CAP * 8, lim, "pool2x2_sum")
+
+
+def case_colsum(dev, M, N, seed=84):
+    """clora_colsum_f16 (bias gradients) against an fp64 column sum, 1e-4 as in case_conv: M > 1024 takes a second row block (fp32
+    atomics join the blocks), N % 128 != 0 a ragged last column block; `out` is added to"""
+    g = torch.Generator().manual_seed(seed)
+    A = rnd((M, N), dev, g)
+    ref = A.double().sum(0)
+    assert rel(K.colsum(A, M, N), ref) < 1e-4, rel(K.colsum(A, M, N), ref)
+    acc = torch.full((N,), 2.0, dtype=f32, device=dev)
+    K.colsum(A, M, N, out=acc)
+    assert rel(acc - 2.0, ref) < 1e-4
 
 
 def case_loss_and_optimizer(dev, n=5000, seed=9):
@@ -849,6 +977,30 @@ def case_loss_and_optimizer(dev, n=5000, seed=9):
             assert float(state[6]) == 1.0 and float(state[3]) == 512.0
         assert rel(p, pt.detach()) < 1e-6, (step, rel(p, pt.detach()))
     assert float(state[2]) == 2.0
+    # the two state slots the host writes (include/clora.h): [11] = data-parallel world size -- the flat buffer holds the SUM over two
+    # ranks (2 g) and the step must land where torch's AdamW fed the mean g lands; [10] = the LR schedule's multiplier -- 0.5 against
+    # torch's AdamW at half the rate.  The middle step is small enough to pass unclipped: clipped steps alone cannot tell whether the
+    # divisor was applied (the clip renormalises whatever it is given), and one unclipped step alone cannot either (Adam's first update is
+    # scale-free).  The unscaled norm the kernel reports in slot 9 is a sum of n fp32 squares in thread / wave / atomic order: 1e-5.
+    for slot, value, what in ((11, 2.0, "world size 2"), (10, 0.5, "lr multiplier 0.5")):
+        st = torch.zeros(16, dtype=f32, device=dev)
+        st[3], st[slot] = 1024.0, value
+        world, lr_mult = (value, 1.0) if slot == 11 else (1.0, value)
+        p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
+        pt = torch.nn.Parameter(p0.clone())
+        opt = torch.optim.AdamW([pt], lr=1e-2 * lr_mult, betas=(0.9, 0.999), weight_decay=1e-2, eps=1e-8)
+        for step, gscale in enumerate((0.1, 0.1 / math.sqrt(n), 0.1)):       # |g| ~ 0.1 sqrt(n) (clipped to 1), ~ 0.1 (not clipped), clipped
+            gr = rnd((n,), dev, g, gscale, f32)
+            summed = gr * (1024.0 * world)                                     # exact: powers of two
+            K.grad_sumsq(summed, st)
+            K.optim_prep(st, 1.0, 0.9, 0.999, True, 2.0, 0.5, 2000)
+            K.adamw_flat(p, summed, m, v, st, 1e-2, 0.9, 0.999, 1e-8, 1e-2)
+            pt.grad = gr.clone()
+            torch.nn.utils.clip_grad_norm_([pt], 1.0)
+            opt.step()
+            norm = float(gr.double().norm())
+            assert abs(float(st[9]) - norm) < 1e-5 * norm, (what, "norm", step, float(st[9]), norm)
+            assert rel(p, pt.detach()) < 1e-6, (what, step, rel(p, pt.detach()))
 
 
 def case_feed_forward_fused(dev, M=200, C=64, seed=12, tile_cfg=0):

@@ -14,7 +14,10 @@ def _emu():
 
 
 @pytest.mark.parametrize("M,N,K,split", [(300, 72, 96, 1), (130, 320, 64, 1), (520, 136, 160, 2), (256, 640, 320, 3),
-                                         (64, 8, 40, 1)])
+                                         (64, 8, 40, 1),
+                                         # the finish pass folds four slabs per trip: one full group, and a group plus a tail of two (K = 768:
+                                         # six real slabs whichever K step the chosen tile has)
+                                         (256, 136, 512, 4), (256, 136, 768, 6)])
 def test_gemm_plain(M, N, K, split):
     KC.case_gemm_plain("cpu", M, N, K, split)
 
@@ -234,7 +237,10 @@ def test_attention_rising_maxima(D):
                                                  (2, 64, 1280, 32, True, False), (1, 256, 2560, 32, True, False), (2, 130, 1920, 32, False, False),
                                                  (1, 600, 640, 32, True, False), (2, 20, 320, 32, True, False), (1, 97, 128, 32, True, False),
                                                  # team plan (HW >= 1024, B * slabs dividing 256): 2 / 4 / 8 slabs, ragged member row ranges
-                                                 (1, 1024, 320, 32, True, False), (2, 1030, 64, 8, False, False), (1, 1100, 640, 32, True, False)])
+                                                 (1, 1024, 320, 32, True, False), (2, 1030, 64, 8, False, False), (1, 1100, 640, 32, True, False),
+                                                 # trainable affine, 2 x 36 row chunks (the last one ragged): 72 per-channel partials, the
+                                                 # eight-loads-in-flight loop of the dgamma / dbeta fold runs before its tail
+                                                 (2, 2300, 64, 8, True, True)])
 def test_groupnorm(B, HW, C, G, silu, train):
     KC.case_groupnorm("cpu", B, HW, C, G, silu, train_params=train)
 
@@ -272,7 +278,8 @@ def test_groupnorm_concat_in_place(B, HW, Ca, Cb, G, silu):
 
 @pytest.mark.parametrize("B,HW,C,Kd,G,split,lora", [(2, 16, 128, 256, 8, 2, False), (2, 64, 320, 320, 32, 3, True), (1, 256, 640, 128, 32, 2, False),
                                                     (2, 300, 64, 96, 8, 2, True),       # two-launch GroupNorm plan: finished first
-                                                    (1, 16, 1280, 256, 32, 4, True), (2, 64, 64, 128, 8, 1, False)])
+                                                    (1, 16, 1280, 256, 32, 4, True), (2, 64, 64, 128, 8, 1, False),
+                                                    (2, 16, 128, 512, 8, 4, False), (2, 16, 128, 768, 8, 6, False)])    # four slabs per trip: a group, a group + tail
 def test_deferred_split_k_finish_in_the_norm_kernels(B, HW, C, Kd, G, split, lora):
     KC.case_deferred_finish("cpu", B, HW, C, Kd, G, split, lora=lora)
 
@@ -297,17 +304,50 @@ def test_geglu():
     KC.case_geglu("cpu", 33, 256)
 
 
-@pytest.mark.parametrize("M,K,N,R,xr", [(300, 320, 64, 4, 0), (128, 72, 40, 8, 32), (70, 96, 32, 20, 0)])
+def test_geglu_past_the_grid_cap():
+    KC.case_geglu("cpu", 4100, 2056)
+
+
+@pytest.mark.parametrize("M,K,N,R,xr", [(300, 320, 64, 4, 0), (128, 72, 40, 8, 32), (70, 96, 32, 20, 0),
+                                        (2113, 72, 520, 4, 0),       # 34 row slabs: the finish pass's eight-loads-in-flight loop, a second column block
+                                        (8200, 72, 1032, 4, 0)])     # lora_up past its 4096-block cap
 def test_lora(M, K, N, R, xr):
     KC.case_lora("cpu", M, K, N, R, x_rows=xr)
+
+
+def test_lora_wgrad_jobs_of_different_sizes_in_one_launch():
+    KC.case_lora_wgrad_multi("cpu")
 
 
 def test_elementwise():
     KC.case_elementwise("cpu")
 
 
+def test_elementwise_past_the_grid_cap():
+    KC.case_elementwise_past_cap("cpu")
+
+
+def test_copies_past_the_grid_cap():
+    KC.case_copies_past_cap("cpu")
+
+
+@pytest.mark.parametrize("B,H,W,C", [(2, 5, 7, 24), (1, 513, 1023, 16)])        # the second: 1022 vectors past the cap
+def test_pool2x2_sum(B, H, W, C):
+    KC.case_pool2x2_sum("cpu", B, H, W, C)
+
+
+@pytest.mark.parametrize("M,N", [(1030, 130), (37, 8)])
+def test_colsum(M, N):
+    KC.case_colsum("cpu", M, N)
+
+
 def test_loss_and_optimizer():
     KC.case_loss_and_optimizer("cpu")
+
+
+def test_loss_and_optimizer_past_the_grid_caps():
+    """mse caps its grid at 256 blocks, grad_sumsq at 1024, AdamW at 4096: 300 elements into the second trip of the widest"""
+    KC.case_loss_and_optimizer("cpu", n=4096 * 256 + 300)
 
 
 @pytest.mark.parametrize("rows,cols", [(5, 64), (9, 1032)])

@@ -182,7 +182,10 @@ def test_attention_rising_maxima(Nq, Nk, D):
                                                  # team plan: the train step's 64x64 / 32x32 maps (bs 4, bs 8), batch 1 / 2, ragged rows
                                                  (4, 4096, 320, 32, True, False), (4, 4096, 640, 32, True, False), (4, 4096, 960, 32, True, False),
                                                  (4, 1024, 320, 32, True, False), (4, 1024, 960, 32, True, False), (8, 4096, 320, 32, True, False),
-                                                 (1, 4096, 320, 32, False, False), (2, 1500, 640, 32, True, False)])
+                                                 (1, 4096, 320, 32, False, False), (2, 1500, 640, 32, True, False),
+                                                 # trainable affine, 2 x 36 row chunks (the last one ragged): 72 per-channel partials, the
+                                                 # eight-loads-in-flight loop of the dgamma / dbeta fold runs before its tail
+                                                 (2, 2300, 64, 8, True, True)])
 def test_groupnorm(B, HW, C, G, silu, train):
     KC.case_groupnorm(DEV, B, HW, C, G, silu, train_params=train)
 
@@ -223,9 +226,19 @@ def test_geglu():
     KC.case_geglu(DEV, 4096, 1280)
 
 
-@pytest.mark.parametrize("M,K,N,R,xr", [(8192, 320, 320, 4, 0), (8192, 320, 320, 8, 4096), (308, 768, 640, 8, 0), (512, 576, 320, 32, 0)])
+def test_geglu_past_the_grid_cap():
+    KC.case_geglu(DEV, 4100, 2056)
+
+
+@pytest.mark.parametrize("M,K,N,R,xr", [(8192, 320, 320, 4, 0), (8192, 320, 320, 8, 4096), (308, 768, 640, 8, 0), (512, 576, 320, 32, 0),
+                                        (2113, 72, 520, 4, 0),       # 34 row slabs: the finish pass's eight-loads-in-flight loop, a second column block
+                                        (8200, 72, 1032, 4, 0)])     # lora_up past its 4096-block cap
 def test_lora(M, K, N, R, xr):
     KC.case_lora(DEV, M, K, N, R, x_rows=xr)
+
+
+def test_lora_wgrad_jobs_of_different_sizes_in_one_launch():
+    KC.case_lora_wgrad_multi(DEV)
 
 
 @pytest.mark.parametrize("kw", [dict(Mc=16384, Cc=320, C_=320, rc=4, n=10), dict(Mc=4096, Cc=640, C_=640, rc=4, n=10),
@@ -249,6 +262,29 @@ def test_elementwise():
 
 def test_loss_and_optimizer():
     KC.case_loss_and_optimizer(DEV, n=100000)
+
+
+def test_loss_and_optimizer_past_the_grid_caps():
+    """mse caps its grid at 256 blocks, grad_sumsq at 1024, AdamW at 4096: 300 elements into the second trip of the widest"""
+    KC.case_loss_and_optimizer(DEV, n=4096 * 256 + 300)
+
+
+@pytest.mark.parametrize("M,N", [(1030, 130), (37, 8)])
+def test_colsum(M, N):
+    KC.case_colsum(DEV, M, N)
+
+
+def test_elementwise_past_the_grid_cap():
+    KC.case_elementwise_past_cap(DEV)
+
+
+def test_copies_past_the_grid_cap():
+    KC.case_copies_past_cap(DEV)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(2, 5, 7, 24), (1, 513, 1023, 16)])        # the second: 1022 vectors past the cap
+def test_pool2x2_sum(B, H, W, C):
+    KC.case_pool2x2_sum(DEV, B, H, W, C)
 
 
 @pytest.mark.parametrize("rows,cols", [(4096, 4096), (1000, 72), (7, 8192)])
