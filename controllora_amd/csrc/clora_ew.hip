@@ -209,7 +209,16 @@ __global__ __launch_bounds__(256) void cast_f16_f32_kernel(const half_t* x, floa
 }
 
 // ---- optimizer -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, size_t n, float* state) {
+// The sum of squares of the flat gradient in a FIXED order: every block leaves its partial in a slot of its own and a second, one-block
+// launch folds the slots (thread t: slots t, t + 256, ...; then wave and block order).  Until then every block added its partial to
+// state[0] with an fp32 atomic, so the sum depended on the order in which the blocks retired: the last bits of the norm differed from
+// launch to launch (4 replays in 5 inside a captured step, 1 eager launch in 5 on an idle chip), and wherever the norm is above
+// max_norm the clip factor carries them into every parameter -- a run did not repeat itself.  The slots belong to the device: calls
+// for one device are issued on one stream at a time (include/clora.h).
+constexpr int kSumsqBlocks = 1024;
+__device__ float g_sumsq_part[kSumsqBlocks * 2];                 // per block: (sum of squares, 1 if it saw an inf or nan)
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, size_t n) {
     __shared__ float red[4];
     __shared__ int bad[4];
     float acc = 0.f;
@@ -224,8 +233,24 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, size_t 
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; bad[threadIdx.x >> 6] = nff > 0.f; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(state + 0, red[0] + red[1] + red[2] + red[3]);
-        if (bad[0] | bad[1] | bad[2] | bad[3]) atomicAdd(state + 1, 1.0f);
+        g_sumsq_part[blockIdx.x * 2] = (red[0] + red[1]) + (red[2] + red[3]);
+        g_sumsq_part[blockIdx.x * 2 + 1] = (bad[0] | bad[1] | bad[2] | bad[3]) ? 1.0f : 0.f;
+    }
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_fold_kernel(int nblocks, float* state) {
+    __shared__ float red[4];
+    __shared__ float bad[4];
+    float acc = 0.f, nb = 0.f;
+    for (int b = threadIdx.x; b < nblocks; b += 256) { acc += g_sumsq_part[b * 2]; nb += g_sumsq_part[b * 2 + 1]; }
+    acc = wave_sum(acc);
+    nb = wave_sum(nb);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; bad[threadIdx.x >> 6] = nb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {                                      // += : state[0] / state[1] accumulate until clora_optim_prep_f32 reads and zeroes them
+        state[0] += (red[0] + red[1]) + (red[2] + red[3]);
+        const float nbad = (bad[0] + bad[1]) + (bad[2] + bad[3]);   // a count of blocks: exact in fp32
+        if (nbad > 0.f) state[1] += nbad;
     }
 }
 
@@ -386,8 +411,9 @@ extern "C" int clora_cast_f16_to_f32(const clora_half* x, float* y, size_t n, vo
 extern "C" int clora_grad_sumsq_f32(const float* g, size_t n, float* state, void* stream) {
     if (!g || !state) return CLORA_ERR_ARG;
     int blocks = ew_grid(n);
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, state);
+    if (blocks > kSumsqBlocks) blocks = kSumsqBlocks;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n);
+    hipLaunchKernelGGL(grad_sumsq_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, blocks, state);
     return clora_check_launch();
 }
 extern "C" int clora_optim_prep_f32(float* state, float max_norm, float beta1, float beta2, int dynamic_scale,

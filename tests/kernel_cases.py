@@ -981,7 +981,7 @@ def case_loss_and_optimizer(dev, n=5000, seed=9):
     # ranks (2 g) and the step must land where torch's AdamW fed the mean g lands; [10] = the LR schedule's multiplier -- 0.5 against
     # torch's AdamW at half the rate.  The middle step is small enough to pass unclipped: clipped steps alone cannot tell whether the
     # divisor was applied (the clip renormalises whatever it is given), and one unclipped step alone cannot either (Adam's first update is
-    # scale-free).  The unscaled norm the kernel reports in slot 9 is a sum of n fp32 squares in thread / wave / atomic order: 1e-5.
+    # scale-free).  The unscaled norm the kernel reports in slot 9 is a sum of n fp32 squares in thread / wave / block order: 1e-5.
     for slot, value, what in ((11, 2.0, "world size 2"), (10, 0.5, "lr multiplier 0.5")):
         st = torch.zeros(16, dtype=f32, device=dev)
         st[3], st[slot] = 1024.0, value
@@ -1001,6 +1001,58 @@ def case_loss_and_optimizer(dev, n=5000, seed=9):
             norm = float(gr.double().norm())
             assert abs(float(st[9]) - norm) < 1e-5 * norm, (what, "norm", step, float(st[9]), norm)
             assert rel(p, pt.detach()) < 1e-6, (what, step, rel(p, pt.detach()))
+
+
+def case_grad_sumsq_reproducible(dev, n=78080, graph=False, seed=93):
+    """clora_grad_sumsq_f32 + clora_optim_prep_f32 on ONE gradient, ten times: sum of squares, reported norm and clip factor are the
+    same BITS every time, and the norm agrees with fp64 to 1e-5 (case_loss_and_optimizer's limit).  The gradient spans six decades
+    and the norm is above max_norm, so the order of the block partials shows in the last bits of the sum and the clip factor carries
+    them to every parameter: with one fp32 atomic per block the norm of this very size (the DreamBooth test's flat LoRA buffer, 305
+    blocks) took 2 - 4 different values in 6 launches on an MI355X, most often inside a replayed graph, and a graphed training run
+    did not repeat itself.  A GEMM in front of every launch makes the blocks start unevenly.  graph (the real library only): the
+    same launches captured once and replayed five times.  The emulator runs blocks one after the other: it checks the arithmetic
+    and the n > 1024 blocks trip, never the ordering."""
+    g = torch.Generator().manual_seed(seed)
+    gr = (rnd((n,), dev, g, 1.0, f32) * torch.pow(10.0, torch.rand(n, generator=g) * 6 - 3).to(dev)).contiguous()
+    A, W = rnd((1024, 64), dev, g), rnd((64, 64), dev, g)
+    norm = float(gr.double().norm())
+    assert norm > 10.0
+
+    st0 = torch.zeros(16, dtype=f32, device=dev)
+    st0[3] = 1.0                                                  # loss scale 1, made once: a scalar write cannot be captured
+
+    def once():
+        st = st0.clone()
+        K.gemm(A, W, 1024, 64, 64)
+        K.grad_sumsq(gr, st)
+        sumsq = st[0:1].clone()
+        K.optim_prep(st, 1.0, 0.9, 0.999, False, 2.0, 0.5, 2000)
+        return sumsq, st
+
+    first = once()
+    assert abs(float(first[1][9]) - norm) < 1e-5 * norm, (float(first[1][9]), norm)
+    assert float(first[1][6]) == 0.0 and 0.0 < float(first[1][5]) < 0.1          # clipped, not skipped
+    runs = [once() for _ in range(9)]
+    if graph:
+        torch.cuda.synchronize()
+        cg = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(cg):
+            captured = once()
+        for _ in range(5):
+            cg.replay()
+            torch.cuda.synchronize()
+            runs.append((captured[0].clone(), captured[1].clone()))
+    seen = sorted({(float(s_), float(st[9]), float(st[5])) for s_, st in [first] + runs})
+    assert len(seen) == 1, f"{len(seen)} different (sum of squares, norm, clip factor) in {len(runs) + 1} launches on one gradient: {seen}"
+    # an inf in the last block's share is counted, whatever the other blocks add
+    bad = gr.clone()
+    bad[n - 3] = float("inf")
+    st = torch.zeros(16, dtype=f32, device=dev)
+    st[3] = 1.0
+    K.grad_sumsq(bad, st)
+    assert float(st[1]) == 1.0
+    K.optim_prep(st, 1.0, 0.9, 0.999, False, 2.0, 0.5, 2000)
+    assert float(st[6]) == 1.0 and float(st[9]) == -1.0 and float(st[0]) == 0.0 and float(st[1]) == 0.0
 
 
 def case_feed_forward_fused(dev, M=200, C=64, seed=12, tile_cfg=0):
@@ -1314,6 +1366,222 @@ def case_groupnorm_offset(dev, B, HW, C, G, offset, silu=False, check=True, eps=
                 worst[k_] = max(worst.get(k_, 0.0), v_)
     assert K.gn_team_errors(x.device) == 0
     return worst
+
+
+
+# ---- the team GroupNorm kernels at narrow slabs and large teams (the VAE's norms), and which plan a call took
+def team_generations(dev):
+    """the 32 generation words of the team GroupNorm exchange state (byte 256 of K.gn_team_state, layout beside kTeamHeader in
+    clora_norm.hip and in INTEGRATION.md) as a list of ints.  A team launch of U = B * slabs units advances exactly the first U words,
+    every other plan advances none: the difference around a call says which plan it took, members = 256 / U."""
+    words = K.gn_team_state(dev)[256:256 + 4 * 32].cpu().view(torch.int32)
+    return [int(w) & 0xFFFFFFFF for w in words]
+
+
+_TEAM_STEP = {}
+
+
+def team_step(dev):
+    """what ONE team launch adds to the generation words of its units: measured once per library on a shape the suite has always run
+    on the team plan, (1, 1024, 320, 32) = 2 slabs of 160 channels (the emulator issues a launch as two passes over the blocks, see
+    gn_team_launch: whatever that makes of the count is read here, not assumed).  The real library: exactly 1."""
+    from controllora_amd import capi
+    key = (str(dev), capi.lib().path)
+    if key not in _TEAM_STEP:
+        g = torch.Generator().manual_seed(90)
+        x = rnd((1, 1024, 320), dev, g)
+        gamma, beta = 1 + 0.2 * rnd((320,), dev, g, dtype=f32), 0.2 * rnd((320,), dev, g, dtype=f32)
+        with options(gn_team=2):
+            before = team_generations(dev)
+            K.groupnorm_fwd(x, gamma, beta, 32, 1e-5, True)
+            after = team_generations(dev)
+        d = [(a - b) & 0xFFFFFFFF for a, b in zip(after, before)]
+        assert d[0] >= 1 and d[:2] == [d[0]] * 2 and d[2:] == [0] * 30, f"(1, 1024, 320, 32) forward is not a 2-unit team launch: {d}"
+        if str(dev) != "cpu":
+            assert d[0] == 1, d
+        _TEAM_STEP[key] = d[0]
+    return _TEAM_STEP[key]
+
+
+class expect_team:
+    """with expect_team(dev, units, launches=1): the block's GroupNorm calls were `launches` team launches of `units` units each
+    (units = 0: none of them took a team kernel), told by the generation words alone"""
+
+    def __init__(self, dev, units, launches=1, what=""):
+        self.dev, self.units, self.launches, self.what = dev, units, launches, what
+
+    def __enter__(self):
+        self.step = team_step(self.dev)
+        self.before = team_generations(self.dev)
+        return self
+
+    def __exit__(self, *exc):
+        if exc[0] is None:
+            after = team_generations(self.dev)
+            d = [(a - b) & 0xFFFFFFFF for a, b in zip(after, self.before)]
+            want = [self.step * self.launches] * self.units + [0] * (32 - self.units)
+            assert d == want, f"{self.what}: expected {self.launches} team launch(es) of {self.units} units ({256 // max(self.units, 1)} members), " \
+                              f"the generation words moved by {d}"
+        return False
+
+
+# (B, HW, C, G, units forward, units backward) at "gn_team" 2, by hand from gn_team_plan (clora_norm.hip); members = 256 / units
+TEAM_NARROW_SHAPES = [
+    (4, 4096, 16, 8, 4, 4),      # the VAE encoder's first norm at resolution 64: CS = 16 (two chunks per row), 64 members, 64 of 256 row lanes own a row
+    (2, 4096, 16, 8, 2, 2),      # ... at the short batch: 128 members over the same generation words and granule slots
+    (4, 1024, 16, 8, 4, 4),      # its 32x32 norms
+    (4, 1024, 32, 8, 4, 4),
+    (1, 4096, 16, 8, 1, 1),      # one unit: 256 members = the sweep's cap at GK = 16 (8 x 512 / 16), 8 granules per thread
+    (2, 1030, 64, 8, 2, 2),      # ragged: 128 members of 9 rows, members 115 .. 127 begin past the last row
+    (4, 4096, 128, 32, 4, 4),    # CS just under 160 with 4-channel groups: GK = 64, the first feasible split is taken
+    (4, 4096, 512, 32, 8, 8),    # the SD-1.5 VAE mid block: two slabs of 256
+    (2, 4096, 512, 32, 4, 4),    # ... one slab would need 128 members at GK = 64 (cap 64): two slabs of 256, 64 members
+]
+
+# ("gn_team", B, HW, C, G, units forward, units backward, run the backward): the 16x16 and 8x8 maps under the levels that admit them
+# (3: HW >= 256 both ways; 4: HW >= 64) and under the default.  A shape whose one-block-per-slab plan holds at most "defer_max_rows"
+# (4) rows per thread keeps that plan at EVERY level (gn_fwd_impl / gn_bwd_impl: fold_shape, so that deferring a producer never changes
+# the bits): (4, 256, 32, 8) and (4, 64, 64, 8) are such shapes and must stay off the team kernels; (4, 256, 64, 8) (8 rows per thread)
+# and (2, 64, 640, 4) (160-channel groups, 6 rows per thread) are the smallest that leave it.
+TEAM_LEVEL_SHAPES = [(3, 4, 256, 32, 8, 0, 0, True), (4, 4, 64, 64, 8, 0, 0, True),
+                     (3, 4, 256, 64, 8, 4, 4, True), (2, 4, 256, 64, 8, 0, 4, True),
+                     (4, 2, 64, 640, 4, 8, 8, True), (3, 2, 64, 640, 4, 0, 0, True), (2, 2, 64, 640, 4, 0, 0, True)]
+
+
+def case_groupnorm_team_narrow(dev, B, HW, C, G, silu, level=2, units=None, units_bwd=None, offset=None, backward=True, eps=1e-5, seed=91):
+    """The team kernels where the UNet shapes never take them: slabs narrower than 160 channels (the planner's first-feasible branch, a
+    thread map in which most row lanes own no row, gn_res_reduce with 8 threads per channel), teams of 128 and 256 members (4 - 8
+    granules per sweeping thread), ragged last members, and the maps that only "gn_team" 3 / 4 put on them.
+      - the plan is asserted, not assumed: `units` (forward) / `units_bwd` team units per launch by the generation words, 0 = no team;
+      - y, statistics (8e-4) and dx with and without dres (2e-3) against fp64 torch on the same fp16 inputs (case_groupnorm's limits);
+      - against "gn_team" 0 on the same inputs: 2e-4 / 1e-5 / 3e-4 (include/clora.h, the table above clora_set_option);
+      - three more identical calls give the bits of the first, and no exchange gave up.
+    Inputs as in case_groupnorm (x * 1.5 + 0.3), or unit variance around `offset` (case_groupnorm_offset: the pivot is shared by all
+    members of a unit)."""
+    units_bwd = units if units_bwd is None else units_bwd
+    team_step(dev)                                               # measured before the level is set: it moves "gn_team" itself
+    g = torch.Generator().manual_seed(seed)
+    if offset is None:
+        x = (rnd((B, HW, C), dev, g).float() * 1.5 + 0.3).half()
+    else:
+        x = (rnd((B, HW, C), dev, g, dtype=f32) + offset).half()
+    gamma, beta = (1 + 0.2 * rnd((C,), dev, g, dtype=f32)), 0.2 * rnd((C,), dev, g, dtype=f32)
+    dy, dres = rnd((B, HW, C), dev, g), rnd((B, HW, C), dev, g)
+    x64 = x.double().clone().requires_grad_(True)
+    y = F.group_norm(x64.permute(0, 2, 1), G, gamma.double(), beta.double(), eps).permute(0, 2, 1)
+    if silu:
+        y = F.silu(y)
+    y.backward(dy.double())
+    xg = x.double().reshape(B, HW, G, C // G)
+    mean, rstd = xg.mean((1, 3)), (xg.var((1, 3), unbiased=False) + eps).rsqrt()
+    tag = f"GN_TEAM_NARROW {(B, HW, C, G)} level={level} offset={offset} silu={silu}"
+
+    def run():
+        with expect_team(dev, units, what=tag + " forward"):
+            out, stats = K.groupnorm_fwd(x, gamma, beta, G, eps, silu)
+        if not backward:
+            return out, stats, None, None
+        with expect_team(dev, units_bwd, 2, what=tag + " backward"):
+            dx, _, _ = K.groupnorm_bwd(x, dy, gamma, beta, stats, G, silu)
+            dx2, _, _ = K.groupnorm_bwd(x, dy, gamma, beta, stats, G, silu, dres=dres)
+        return out, stats, dx, dx2
+
+    with options(gn_team=level):
+        out, stats, dx, dx2 = run()
+        again = [run() for _ in range(3)]
+    with options(gn_team=0), expect_team(dev, 0, what=tag + " gn_team=0"):
+        out0, stats0 = K.groupnorm_fwd(x, gamma, beta, G, eps, silu)
+        dx0 = K.groupnorm_bwd(x, dy, gamma, beta, stats0, G, silu, dres=dres)[0] if backward else None
+    errs = dict(y=rel64(out, y), mean=rel64(stats[..., 0], mean), rstd=rel64(stats[..., 1], rstd))
+    across = dict(y=rel64(out, out0), stats=rel64(stats, stats0))
+    if backward:
+        errs.update(dx=rel64(dx, x64.grad), dx_res=rel64(dx2, x64.grad + dres.double()))
+        across.update(dx=rel64(dx2, dx0))
+    print(tag, "units", (units, units_bwd), " ".join(f"{k_}={v_:.2e}" for k_, v_ in errs.items()),
+          "| vs gn_team=0", " ".join(f"{k_}={v_:.2e}" for k_, v_ in across.items()))
+    assert errs["y"] < 8e-4 and errs["mean"] < 8e-4 and errs["rstd"] < 8e-4, errs
+    no_outliers(out, y, tag + " y")
+    assert across["y"] < 2e-4 and across["stats"] < 1e-5, across
+    if backward:
+        assert errs["dx"] < 2e-3 and errs["dx_res"] < 2e-3, errs
+        no_outliers(dx, x64.grad, tag + " dx")
+        assert across["dx"] < 3e-4, across
+    for i, rerun in enumerate(again):
+        for name, a, b_ in zip(("y", "stats", "dx", "dx + dres"), rerun, (out, stats, dx, dx2)):
+            assert a is None or torch.equal(a, b_), f"{tag}: {name} of identical call {i + 2} differs from the first " \
+                                                    f"({int((a != b_).sum())} elements, rel {rel64(a, b_):.2e})"
+    assert K.gn_team_errors(dev) == 0
+    return errs
+
+
+def case_groupnorm_team_alternating(dev, graph=False):
+    """The launch sequence of a training run whose epochs end in a short batch (the VAE encoder's team norms at resolution 64, batch
+    4, 2, 4, 2): 4 units of 64 members and 2 units of 128 members alternate over the same generation words and granule slots, a GEMM
+    between the launches so that workgroups start unevenly.  Four repetitions of forward + backward at (4, 4096, 16), (4, 1024, 32),
+    (2, 4096, 16), (2, 1024, 32), G = 8:
+      - every repetition gives the bits of the first, and the generation words moved as the plan says (units 0, 1 by every launch,
+        units 2, 3 by the batch-4 launches only);
+      - the same sequence on a freshly zeroed state gives the same bits (the old state is put back, never freed: graphs hold it);
+      - graph (the real library only): the batch-4 pair captured in one graph and replayed five times with eager batch-2 launches
+        between the replays; every replay and every eager launch gives the bits of the first eager pass.
+    A determinism check of 4 + 4 + 5 rounds, not a loop that hunts for a failure."""
+    g = torch.Generator().manual_seed(92)
+    G = 8
+    data = []
+    for B, HW, C in ((4, 4096, 16), (4, 1024, 32), (2, 4096, 16), (2, 1024, 32)):
+        x, dy = (rnd((B, HW, C), dev, g).float() * 1.5 + 0.3).half(), rnd((B, HW, C), dev, g)
+        gamma, beta = 1 + 0.2 * rnd((C,), dev, g, dtype=f32), 0.2 * rnd((C,), dev, g, dtype=f32)
+        data.append((x, dy, gamma, beta))
+    A, W = rnd((1024, 64), dev, g), rnd((64, 64), dev, g)
+
+    def launches(items):
+        outs = []
+        for x, dy, gamma, beta in items:
+            y, st = K.groupnorm_fwd(x, gamma, beta, G, 1e-5, True)
+            K.gemm(A, W, 1024, 64, 64)
+            dx, _, _ = K.groupnorm_bwd(x, dy, gamma, beta, st, G, True)
+            outs += [y, st, dx]
+        return outs
+
+    def sequence(what):
+        step = team_step(dev)
+        before = team_generations(dev)
+        reps = [launches(data) for _ in range(4)]
+        d = [(a - b) & 0xFFFFFFFF for a, b in zip(team_generations(dev), before)]
+        assert d == [32 * step] * 2 + [16 * step] * 2 + [0] * 28, (what, d)
+        for r, rep in enumerate(reps[1:]):
+            for i, (a, b_) in enumerate(zip(rep, reps[0])):
+                assert torch.equal(a, b_), f"{what}: repetition {r + 2}, output {i} (shape {tuple(a.shape)}) differs from the first repetition " \
+                                           f"in {int((a != b_).sum())} elements"
+        return reps[0]
+
+    step = team_step(dev)
+    with options(gn_team=2):
+        first = sequence("persistent state")
+        key = K._dev_key(dev)
+        old = K._gn_team[key]
+        K._gn_team[key] = torch.zeros_like(old)
+        try:
+            fresh = sequence("zeroed state")
+            assert team_generations(dev) == [32 * step] * 2 + [16 * step] * 2 + [0] * 28
+            assert K.gn_team_errors(dev) == 0
+        finally:
+            K._gn_team[key] = old
+        for i, (a, b_) in enumerate(zip(fresh, first)):
+            assert torch.equal(a, b_), f"zeroed state: output {i} differs from the persistent state's in {int((a != b_).sum())} elements"
+        if graph:
+            torch.cuda.synchronize()
+            cg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(cg):
+                captured = launches(data[:2])
+            for rnd_ in range(5):
+                cg.replay()
+                eager = launches(data[2:])
+                torch.cuda.synchronize()
+                for i, (a, b_) in enumerate(zip(captured + eager, first)):
+                    assert torch.equal(a, b_), f"round {rnd_}: output {i} ({'replay' if i < 6 else 'eager'}) differs from the first eager pass " \
+                                               f"in {int((a != b_).sum())} elements"
+    assert K.gn_team_errors(dev) == 0
 
 
 def case_lora_down_mode(dev, mode, M, Kd):

@@ -27,7 +27,12 @@ clora_lora.hip
   down_r2          (control) lora_down drops the row limit r2 of the second input
 clora_epilogue.h
   finish_b0        finish_chunk8: the 4-slabs-in-flight loop adds b[0] for every slab of the group
-  finish_tail      finish_chunk8: the tail after a full group reads slab 4 for every later slab (columns 4..7)"""
+  finish_tail      finish_chunk8: the tail after a full group reads slab 4 for every later slab (columns 4..7)
+
+Not in the table, because no mutant can express it here: grad_sumsq_kernel's former one-fp32-atomic-per-block sum (the gradient norm
+followed the order in which blocks retired).  The emulator runs the blocks of a launch one after the other, so that kernel gives the
+same bits on every launch; tests/kernel_cases.py::case_grad_sumsq_reproducible fails on it on the GPU only (4 and 9 different norms in
+15 launches on an MI355X)."""
 import concurrent.futures
 import contextlib
 import glob

@@ -269,6 +269,28 @@ def test_groupnorm_wide_groups(B, HW, C, G):
     KC.case_groupnorm("cpu", B, HW, C, G, True, seed=B + HW)
 
 
+# the C = 512 shapes (64 channel chunks per row, 8 and 16 rows per thread) are left to the GPU: 25 s each here
+@pytest.mark.parametrize("B,HW,C,G,units,units_bwd", [s for s in KC.TEAM_NARROW_SHAPES if s[2] < 512])
+def test_groupnorm_team_narrow_slabs_and_large_teams(B, HW, C, G, units, units_bwd):
+    """the VAE's norms on the team kernels (CS < 160, 64 / 128 / 256 members, ragged members), each with its plan asserted; blocks run
+    one after the other here: arithmetic, indexing and the plan, not ordering or visibility"""
+    KC.case_groupnorm_team_narrow("cpu", B, HW, C, G, HW != 1030, units=units, units_bwd=units_bwd)
+
+
+def test_groupnorm_team_narrow_away_from_zero_mean():
+    for B in (4, 2):
+        KC.case_groupnorm_team_narrow("cpu", B, 4096, 16, 8, False, units=B, offset=10.0)
+
+
+@pytest.mark.parametrize("level,B,HW,C,G,units,units_bwd,backward", KC.TEAM_LEVEL_SHAPES)
+def test_groupnorm_team_option_levels(level, B, HW, C, G, units, units_bwd, backward):
+    KC.case_groupnorm_team_narrow("cpu", B, HW, C, G, True, level=level, units=units, units_bwd=units_bwd, backward=backward)
+
+
+def test_groupnorm_team_alternating_64_and_128_members():
+    KC.case_groupnorm_team_alternating("cpu")
+
+
 @pytest.mark.parametrize("B,HW,Ca,Cb,G,silu", [(2, 64, 320, 320, 32, True), (1, 256, 640, 320, 32, True), (2, 16, 1280, 1280, 32, True),
                                                (1, 300, 64, 32, 8, False), (2, 9, 1280, 640, 32, True), (1, 1024, 320, 640, 32, True),
                                                (3, 37, 8, 56, 8, True)])
@@ -343,6 +365,12 @@ def test_colsum(M, N):
 
 def test_loss_and_optimizer():
     KC.case_loss_and_optimizer("cpu")
+
+
+@pytest.mark.parametrize("n", [78080, 1024 * 256 + 300])
+def test_grad_norm_is_the_same_bits_on_every_launch(n):
+    """the DreamBooth test's flat LoRA buffer (305 blocks) and one element count past the 1024-block cap of clora_grad_sumsq_f32"""
+    KC.case_grad_sumsq_reproducible("cpu", n)
 
 
 def test_loss_and_optimizer_past_the_grid_caps():

@@ -264,6 +264,12 @@ def test_loss_and_optimizer():
     KC.case_loss_and_optimizer(DEV, n=100000)
 
 
+@pytest.mark.parametrize("n", [78080, 1024 * 256 + 300])
+def test_grad_norm_is_the_same_bits_on_every_launch(n):
+    """the DreamBooth test's flat LoRA buffer (305 blocks) and one element count past the 1024-block cap of clora_grad_sumsq_f32"""
+    KC.case_grad_sumsq_reproducible(DEV, n, graph=True)
+
+
 def test_loss_and_optimizer_past_the_grid_caps():
     """mse caps its grid at 256 blocks, grad_sumsq at 1024, AdamW at 4096: 300 elements into the second trip of the widest"""
     KC.case_loss_and_optimizer(DEV, n=4096 * 256 + 300)
@@ -477,6 +483,28 @@ def test_groupnorm_team_exchange_under_graph_replay_and_changing_geometry():
         for a, b in zip(captured, first):
             assert torch.equal(a, b)
     assert K.gn_team_errors(DEV) == 0
+
+
+@pytest.mark.parametrize("B,HW,C,G,units,units_bwd", KC.TEAM_NARROW_SHAPES)
+def test_groupnorm_team_narrow_slabs_and_large_teams(B, HW, C, G, units, units_bwd):
+    """the VAE's norms on the team kernels (CS < 160, 64 / 128 / 256 members, ragged members), each with its plan asserted"""
+    KC.case_groupnorm_team_narrow(DEV, B, HW, C, G, HW != 1030, units=units, units_bwd=units_bwd)
+
+
+def test_groupnorm_team_narrow_away_from_zero_mean():
+    """mean 10 std at the 64- and 128-member geometries: every member of a unit subtracts the same pivot"""
+    for B in (4, 2):
+        KC.case_groupnorm_team_narrow(DEV, B, 4096, 16, 8, False, units=B, offset=10.0)
+
+
+@pytest.mark.parametrize("level,B,HW,C,G,units,units_bwd,backward", KC.TEAM_LEVEL_SHAPES)
+def test_groupnorm_team_option_levels(level, B, HW, C, G, units, units_bwd, backward):
+    """"gn_team" 3 / 4 put the 16x16 / 8x8 maps on the team kernels; at the default the same call must not take them"""
+    KC.case_groupnorm_team_narrow(DEV, B, HW, C, G, True, level=level, units=units, units_bwd=units_bwd, backward=backward)
+
+
+def test_groupnorm_team_alternating_64_and_128_members():
+    KC.case_groupnorm_team_alternating(DEV, graph=True)
 
 
 @pytest.mark.parametrize("M,N,K_,split,tile,lora", [(16384, 320, 320, 1, 0, False), (16384, 320, 320, 1, 55, True), (1024, 1280, 1280, 3, 0, False),
