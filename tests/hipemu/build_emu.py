@@ -51,7 +51,7 @@ def units_including(src_dir: str, file_name: str) -> set:
 
 def build_mutant(out_dir: str, file_name: str, edits) -> str:
     """The emulator library with some source lines of ``csrc/<file_name>`` replaced (``edits`` = [(old, new)], each ``old`` must
-    occur exactly once): used by the
+    occur exactly once, or [(old, new, n)] for the n-th occurrence, counted from 0, of text that occurs several times): used by the
     tests that prove the emulator's pessimistic LDS-DMA model catches a weakened ``s_waitcnt`` (tests/test_emu_async_model.py) and that
     the kernel cases fail on a subtly wrong kernel (tests/test_attention_mutants_emu.py, tests/test_kernel_mutants_emu.py).
     ``file_name`` may be a header of ``csrc``: every translation unit that includes it (units_including) is recompiled then, and an
@@ -62,7 +62,15 @@ def build_mutant(out_dir: str, file_name: str, edits) -> str:
     shutil.copytree(os.path.join(ROOT, "include"), os.path.join(out_dir, "include"))
     path = os.path.join(src_dir, file_name)
     text = open(path).read()
-    for old, new in edits:
+    for old, new, *nth in edits:
+        if nth:                                                   # (old, new, n): the n-th occurrence (from 0) of a line several kernels share
+            at = -1
+            for _ in range(nth[0] + 1):
+                at = text.find(old, at + 1)
+                if at < 0:
+                    raise ValueError(f"{file_name}: mutation anchor {old!r} occurs {text.count(old)} times, occurrence {nth[0]} wanted")
+            text = text[:at] + new + text[at + len(old):]
+            continue
         if text.count(old) != 1:
             raise ValueError(f"{file_name}: mutation anchor {old!r} occurs {text.count(old)} times")
         text = text.replace(old, new)

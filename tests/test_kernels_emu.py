@@ -17,9 +17,26 @@ def _emu():
                                          (64, 8, 40, 1),
                                          # the finish pass folds four slabs per trip: one full group, and a group plus a tail of two (K = 768:
                                          # six real slabs whichever K step the chosen tile has)
-                                         (256, 136, 512, 4), (256, 136, 768, 6)])
+                                         (256, 136, 512, 4), (256, 136, 768, 6),
+                                         # M * N / 8 = 529,416 chunks > 2048 blocks x 256 (finish_or_defer): splitk_finish_kernel takes a second trip of
+                                         # its grid-stride loop for the rows from 4064 on; short K
+                                         (4104, 1032, 64, 2), (4104, 1032, 64, 3)])
 def test_gemm_plain(M, N, K, split):
     KC.case_gemm_plain("cpu", M, N, K, split)
+
+
+def test_elementwise_limit_sees_one_wrong_element():
+    """the helper itself: on a case_gemm_plain output from the real sources, ONE element moved by 0.05 stays under the norm-wise 6e-4
+    and fails the derived elementwise limit, which names it"""
+    out, ref, mag = KC.case_gemm_plain("cpu", 300, 72, 96, 1)
+    bad = out.clone()
+    bad[137, 41] += 0.05
+    assert KC.rel(out, ref) < KC.rel(bad, ref) < 6e-4
+    with pytest.raises(AssertionError, match=r"planted: 1 of 21600 elements past the derived limit; worst at \(137, 41\)"):
+        KC.within_limit(bad, ref, mag, 96 + 1, what="planted")
+    bad[137, 41] = float("nan")                              # an element no launch wrote
+    with pytest.raises(AssertionError, match=r"worst at \(137, 41\)"):
+        KC.within_limit(bad, ref, mag, 96 + 1, what="planted")
 
 
 @pytest.mark.parametrize("split", [1, 2])
@@ -43,13 +60,38 @@ def test_conv_wgrad_patch_kernel_stride2(Bn, H, W, Ci, Co):
     KC.case_conv_wgrad_patch("cpu", Bn, H, W, Ci, Co, stride=2)
 
 
-@pytest.mark.parametrize("Bn,H,W,Ci,Co", [(1, 3, 128, 32, 32), (2, 2, 128, 32, 64), (1, 2, 128, 64, 32), (1, 5, 256, 32, 24), (2, 3, 128, 8, 32), (1, 2, 128, 8, 48)])
+@pytest.mark.parametrize("Bn,H,W,Ci,Co", [(1, 3, 128, 32, 32), (2, 2, 128, 32, 64), (1, 2, 128, 64, 32), (1, 5, 256, 32, 24), (2, 3, 128, 8, 32), (1, 2, 128, 8, 48),
+                                          # H = 17: row chunks of 8, 8 and 1 (KC.case_conv_strip); 32 / 64 / 8 input channels (the 8-channel kernel also
+                                          # as the dgrad of a 32 -> 8 convolution), two images, two 128-pixel segments
+                                          (1, 17, 128, 32, 32), (2, 17, 128, 64, 32), (1, 17, 256, 32, 64), (2, 17, 128, 8, 32), (1, 17, 256, 32, 8),
+                                          (1, 17, 128, 8, 64)])
 def test_conv_strip_kernel(Bn, H, W, Ci, Co):
     KC.case_conv_strip("cpu", Bn, H, W, Ci, Co)
 
 
 def test_conv_small_channels():
     KC.case_conv("cpu", 1, 16, 16, 8, 32)       # hint-encoder conv_in shape class (3 -> padded 8 channels)
+
+
+@pytest.mark.parametrize("shapes", [((232, 256, 256),), ((229, 253, 256), (16, 3, 8), (64, 32, 32))])
+def test_conv_weight_pack_and_wgrad_unpack_past_their_caps(shapes):
+    """Co * 9 * Cip = 534,528 / 527,616 > 2048 x 256 (1024 x 256 in the multi-job forms); padded input (253 -> 256) and output (229 -> 232)
+    channels; one multi-job launch whose jobs differ in size"""
+    KC.case_conv_pack_unpack_past_cap("cpu", shapes)
+
+
+@pytest.mark.parametrize("Co", [72, 136])
+def test_conv_wgrad_gather_kernel_several_channel_tiles(Co):
+    """conv_wgrad_kernel (16 input channels: never the patch kernel) with two and three 64-wide output-channel tiles, the last one
+    ragged (8 channels): dW with and without the bias column, conv_wgrad_into and conv_wgrad_staged under the elementwise limit"""
+    KC.case_conv("cpu", 1, 8, 8, 16, Co)
+
+
+@pytest.mark.parametrize("tile", [72, 76])
+def test_conv_patch_kernel_uneven_split(tile):
+    """192 channels = three 64-channel slabs: split-K 2 gives 2 + 1 slabs, the second split's range is clamped to the slab count (the
+    other CPU shapes have one or two slabs, which every split count divides: tests/test_kernel_mutants_emu.py patch_clamp)"""
+    KC.case_conv_patch("cpu", 1, 8, 8, 192, 64, tile)
 
 
 @pytest.mark.parametrize("tile", KC.ALL_TILE_CFGS)

@@ -21,7 +21,9 @@ def _native_lib_loaded():
 
 
 @pytest.mark.parametrize("M,N,K,split", [(300, 72, 96, 1), (4096, 960, 320, 1), (1024, 1280, 1280, 1), (256, 1280, 1280, 4),
-                                         (308, 640, 768, 1), (4096, 2560, 320, 1), (1024, 320, 1280, 2), (64, 8, 40, 1)])
+                                         (308, 640, 768, 1), (4096, 2560, 320, 1), (1024, 320, 1280, 2), (64, 8, 40, 1),
+                                         # M * N / 8 just past 2048 blocks x 256: the second trip of splitk_finish_kernel's grid-stride loop alone
+                                         (4104, 1032, 64, 2), (4104, 1032, 64, 3)])
 def test_gemm_plain(M, N, K, split):
     KC.case_gemm_plain(DEV, M, N, K, split)
 
@@ -51,13 +53,37 @@ def test_conv_wgrad_patch_kernel_stride2(Bn, H, W, Ci, Co):
     KC.case_conv_wgrad_patch(DEV, Bn, H, W, Ci, Co, stride=2)
 
 
-@pytest.mark.parametrize("Bn,H,W,Ci,Co", [(4, 512, 512, 32, 32), (4, 256, 256, 32, 64), (2, 37, 384, 64, 32), (1, 5, 128, 32, 24), (4, 512, 512, 8, 32), (1, 6, 256, 8, 64)])
+@pytest.mark.parametrize("Bn,H,W,Ci,Co", [(4, 512, 512, 32, 32), (4, 256, 256, 32, 64), (2, 37, 384, 64, 32), (1, 5, 128, 32, 24), (4, 512, 512, 8, 32), (1, 6, 256, 8, 64),
+                                          # H = 17: row chunks of 8, 8 and 1 (KC.case_conv_strip), the shapes of the CPU suite
+                                          (1, 17, 128, 32, 32), (2, 17, 128, 64, 32), (1, 17, 256, 32, 64), (2, 17, 128, 8, 32), (1, 17, 256, 32, 8),
+                                          (1, 17, 128, 8, 64)])
 def test_conv_strip_kernel(Bn, H, W, Ci, Co):
     KC.case_conv_strip(DEV, Bn, H, W, Ci, Co)
 
 
 def test_conv_small_channels():
     KC.case_conv(DEV, 1, 64, 64, 8, 32)
+
+
+@pytest.mark.parametrize("shapes", [((232, 256, 256),), ((229, 253, 256), (16, 3, 8), (64, 32, 32))])
+def test_conv_weight_pack_and_wgrad_unpack_past_their_caps(shapes):
+    """Co * 9 * Cip = 534,528 / 527,616 > 2048 x 256 (1024 x 256 in the multi-job forms); padded input (253 -> 256) and output (229 -> 232)
+    channels; one multi-job launch whose jobs differ in size"""
+    KC.case_conv_pack_unpack_past_cap(DEV, shapes)
+
+
+@pytest.mark.parametrize("Co", [72, 136])
+def test_conv_wgrad_gather_kernel_several_channel_tiles(Co):
+    """conv_wgrad_kernel (16 input channels: never the patch kernel) with two and three 64-wide output-channel tiles, the last one
+    ragged (8 channels): dW with and without the bias column, conv_wgrad_into and conv_wgrad_staged under the elementwise limit"""
+    KC.case_conv(DEV, 1, 8, 8, 16, Co)
+
+
+@pytest.mark.parametrize("tile", [72, 76])
+def test_conv_patch_kernel_uneven_split(tile):
+    """192 channels = three 64-channel slabs: split-K 2 gives 2 + 1 slabs, the second split's range is clamped to the slab count (the
+    other CPU shapes have one or two slabs, which every split count divides: tests/test_kernel_mutants_emu.py patch_clamp)"""
+    KC.case_conv_patch(DEV, 1, 8, 8, 192, 64, tile)
 
 
 @pytest.mark.parametrize("tile", KC.ALL_TILE_CFGS)
@@ -73,19 +99,20 @@ def test_gemm_tile_configs(tile):
 @pytest.mark.parametrize("M,N,K,split", [(4096, 2560, 320, 1), (1000, 520, 1096, 2), (16384, 1280, 320, 1), (513, 264, 8200, 1), (2048, 2048, 2048, 1)])
 def test_gemm_eight_phase_tile(M, N, K, split):
     """tile_cfg 59 (gemm_8p_kernel: 256x256 tile, two wave rows one barrier apart, half-tile LDS-DMA seven ahead): the level-0
-    FeedForward shapes, ragged M / N / K tail, split-K, a long K; elementwise outlier guard and repeat-launch bit equality inside
+    FeedForward shapes, ragged M / N / K tail, split-K, a long K; elementwise outlier guard, the derived elementwise limit (fp64 reference) and repeat-launch bit equality inside
     the case (a rare early read of a staged buffer would show as a few wrong tiles)"""
     import math
     import torch
     from controllora_amd import kernels as K_
     g = torch.Generator().manual_seed(M + K)
     A, B = KC.rnd((M, K), DEV, g), KC.rnd((N, K), DEV, g, 1 / math.sqrt(K))
-    ref = A.float() @ B.float().T
+    ref, mag = KC.d64(A) @ KC.d64(B).T, KC.d64(A).abs() @ KC.d64(B).abs().T
     first = None
     for _ in range(4):
         out = K_.gemm(A, B, M, N, K, split_k=split, tile_cfg=59, _tuned=False)
         assert KC.rel(out, ref) < 6e-4
         KC.no_outliers(out, ref)
+        KC.within_limit(out, ref, mag, K + split, what=f"gemm_eight_phase: {(M, N, K, split)}")
         if first is None:
             first = out.clone()
         assert torch.equal(out, first)
