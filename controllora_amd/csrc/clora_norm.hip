@@ -3,10 +3,18 @@
 // HBM-bound kernels: every pass reads/writes whole 16-byte channel chunks of
 // full rows, so global traffic is coalesced regardless of how channels split into groups
 // (C/32 = 10 channels per group at C=320 is not a multiple of the 8-channel load width).
-//   GroupNorm forward : partial (sum, sumsq per (b, row-chunk, group), deterministic block reduce) -> apply
-//                       (each block re-folds the partials of its batch element and keeps its per-channel
-//                       scale/shift in registers: two launches, no atomics, no coefficient table)
-//   GroupNorm backward: partial (s1 = sum dy*gamma, s2 = sum dy*gamma*xhat) -> apply (dx = k1*dy' + k2*x + k3)
+//   GroupNorm, forward and backward, in three forms that compute the same per-thread arithmetic over different row windows (the
+//   forward's is written once: GN_ACCUM8, gn_stats_from_moments, gn_affine8, GN_NORM8; the backward's is written out per kernel):
+//     two-launch : gn_*_partial_kernel (per (b, row chunk, group) sums, deterministic block reduce) -> gn_*_apply2_kernel (each block
+//                  re-folds the partials of its batch element and keeps its per-channel coefficients in registers; no atomics, no
+//                  coefficient table).  Any shape, trainable affine included; needs the workspace.
+//     resident   : gn_*_resident_kernel, one block per (batch element, channel slab) keeps all rows of the slab in registers between the
+//                  statistics and the apply: the 8x8 / 16x16 (at 512 threads 32x32) maps.  Can fold a deferred split-K producer (DEF).
+//     team       : gn_*_team_kernel, a team of blocks per (batch element, slab), each member with its rows in registers, exchanging
+//                  per-group sums inside the launch: the 32x32 / 64x64 maps.
+//   gn_launch_plan chooses the form (and whether a deferred producer is folded or finished first) for both directions;
+//   gn_resident_launch / gn_two_launch / gn_team_launch map the plan to an instantiation.
+//   forward : y = (x - mean) * rstd * gamma + beta (+ SiLU);  backward: dx = k1*dy' + k2*x + k3 with s1 = sum dy*gamma, s2 = sum dy*gamma*xhat
 //   LayerNorm         : one wave per row, the row lives in registers (two-pass variance), no workspace.
 #include <stdlib.h>
 #include "clora_common.h"
@@ -117,6 +125,60 @@ __device__ __forceinline__ void gn_pivots8(const GnArgs& a, int b, int ch0, int 
     }
 }
 
+// ---- the forward's per-thread arithmetic of one 8-channel chunk of one row, shared by the three forms.  A form decides which rows a
+// thread owns and how it loads them; everything it then computes per row is here, once.  (w / m: the LO remainder chunk and its weight.)
+//
+// The two forward blocks that touch every element are macros, not functions.  hipcc builds with -ffp-contract=fast and decides per
+// instantiation whether q += f * f (and y = x * sc + sh) becomes one fma or a multiply and a packed add, and that choice moves when
+// the block sits behind a call boundary, forceinline or not: as functions these two changed the fused / unfused mix, and so the bits
+// of the statistics, in 18 of the 33 forward instantiations (and occupancy or scratch in 6; profiles/norm_refactor_resources.txt).
+// Expanded in place they keep what was checked against the block written out: the same count of every floating-point opcode in
+// every forward instantiation (register allocation and scheduling do move: the ISA of the resident and team forward kernels is not
+// identical), the same occupancy, and byte-equal outputs on an MI355X (profiles/norm_refactor_bits.txt).  The other helpers below
+// are functions: they passed the same three checks.
+//
+// forward sums: (x - pivot) and its square into s / q; rows outside the thread's window add zero (ok = false)
+#define GN_ACCUM8(LO, v, w, m, piv, ok, s, q)                                                                                    \
+    if constexpr (LO) {                                                                                                          \
+        float xv[8];                                                                                                             \
+        gn_val8(v, w, m, xv);                                                                                                    \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) { const float f = (ok) ? xv[e] - (piv)[e] : 0.f; (s)[e] += f; (q)[e] += f * f; } \
+    } else {                                                                                                                     \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) { const float f = (ok) ? (float)(v)[e] - (piv)[e] : 0.f; (s)[e] += f; (q)[e] += f * f; } \
+    }
+// o = the row's chunk of y: normalise, optional SiLU, round
+#define GN_NORM8(LO, v, w, m, sc, sh, silu, o)                                                                                   \
+    {                                                                                                                            \
+        float xv[8];                                                                                                             \
+        if constexpr (LO) gn_val8(v, w, m, xv);                                                                                  \
+        _Pragma("unroll") for (int e = 0; e < 8; ++e) {                                                                          \
+            float yv = (LO ? xv[e] : (float)(v)[e]) * (sc)[e] + (sh)[e];                                                         \
+            if (silu) yv = silu_f(yv);                                                                                           \
+            (o)[e] = (half_t)yv;                                                                                                 \
+        }                                                                                                                        \
+    }
+// (E[x - P], E[(x - P)^2], P) -> (mean, rstd), see gn_pivot
+__device__ __forceinline__ void gn_stats_from_moments(float dm, float q, float pivot, float eps, float& mean, float& rstd) {
+    mean = pivot + dm;
+    float var = q - dm * dm;
+    var = var < 0.f ? 0.f : var;
+    rstd = rsqrtf(var + eps);
+}
+// y = x * sc + sh: mr = (mean, rstd) pairs of the groups, cl0 = the chunk's first channel counted from the first group of mr
+__device__ __forceinline__ void gn_affine8(const float* mr, int cl0, int cpg, const float (&gam)[8], const float (&bet)[8],
+                                           float (&sc)[8], float (&sh)[8]) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int g = (cl0 + e) / cpg;
+        sc[e] = mr[g * 2 + 1] * gam[e];
+        sh[e] = bet[e] - mr[g * 2] * sc[e];
+    }
+}
+__device__ __forceinline__ void gn_unpack8(const floatx4& a, const floatx4& b, float (&f)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { f[e] = a[e]; f[4 + e] = b[e]; }
+}
+
 // thread -> (row lane, first column chunk, column stride)
 __device__ __forceinline__ void gn_thread_map(int t, int CH, int& rl, int& nrl, int& c0, int& cstep, bool& active) {
     if (CH >= 256) { rl = 0; nrl = 1; c0 = t; cstep = 256; active = true; }
@@ -220,18 +282,9 @@ __global__ __launch_bounds__(256) void gn_fwd_partial_kernel(GnArgs p) {
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
                     CLORA_KEEP(v[u][j]);
-                    if constexpr (LO) {
-                        CLORA_KEEP(w[u][j]);
-                        if (c0 + j * cstep < CH) {
-                            float xv[8];
-                            gn_val8(v[u][j], w[u][j], lcol[j].m, xv);
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
-                        }
-                    } else
+                    if constexpr (LO) CLORA_KEEP(w[u][j]);
                     if (c0 + j * cstep < CH) {                   // thread-constant
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[u][j][e] - piv[j][e] : 0.f; s[j][e] += f; q[j][e] += f * f; }
+                        GN_ACCUM8(LO, v[u][j], w[u][j], lcol[j].m, piv[j], ok, s[j], q[j])
                     }
                 }
             }
@@ -343,11 +396,9 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
     const int CH = p.CS / 8, cpg = p.C / p.G;
     gn_fold_groups(p, b, t, mr, 1.0f / ((float)p.HW * (float)cpg));
     __syncthreads();
-    if (t < p.G) {                                  // (E[x - P], E[(x - P)^2]) -> (mean, rstd), see gn_pivot
-        const float dm = mr[t * 2], mean = gn_pivot(p, b, t * cpg) + dm;
-        float var = mr[t * 2 + 1] - dm * dm;
-        var = var < 0.f ? 0.f : var;
-        const float rstd = rsqrtf(var + p.eps);
+    if (t < p.G) {
+        float mean, rstd;
+        gn_stats_from_moments(mr[t * 2], mr[t * 2 + 1], gn_pivot(p, b, t * cpg), p.eps, mean, rstd);
         mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         if (chunk == 0 && blockIdx.y == 0) { p.stats[((size_t)b * p.G + t) * 2] = mean; p.stats[((size_t)b * p.G + t) * 2 + 1] = rstd; }
@@ -357,14 +408,13 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
     gn_thread_map(t, CH, rl, nrl, c0, cstep, active);
     float sc[NJ][8], sh[NJ][8];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j)
+    for (int j = 0; j < NJ; ++j) {
+        const int cc = c0 + j * cstep, ch0 = cb + (cc < CH ? cc : 0) * 8;
+        float gam[8], bet[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int cc = c0 + j * cstep;
-            const int ch = cb + (cc < CH ? cc : 0) * 8 + e, g = ch / cpg;
-            sc[j][e] = mr[g * 2 + 1] * p.gamma[ch];
-            sh[j][e] = p.beta[ch] - mr[g * 2] * sc[j][e];
-        }
+        for (int e = 0; e < 8; ++e) { gam[e] = p.gamma[ch0 + e]; bet[e] = p.beta[ch0 + e]; }
+        gn_affine8(mr, ch0, cpg, gam, bet, sc[j], sh[j]);
+    }
     if (!active) return;
     const int r_beg = chunk * p.rows_per_chunk;
     const int r_end = (r_beg + p.rows_per_chunk < p.HW) ? r_beg + p.rows_per_chunk : p.HW;
@@ -399,15 +449,9 @@ __global__ __launch_bounds__(256) void gn_fwd_apply2_kernel(GnArgs p) {
             for (int j = 0; j < NJ; ++j) {
                 const int cc = c0 + j * cstep;
                 CLORA_KEEP(v[u][j]);
-                float xv[8];
-                if constexpr (LO) { CLORA_KEEP(w[u][j]); gn_val8(v[u][j], w[u][j], lcol[j].m, xv); }
+                if constexpr (LO) CLORA_KEEP(w[u][j]);
                 half8 o;                                         // computed unconditionally (keeps the loads above the branch) ...
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float yv = (LO ? xv[e] : (float)v[u][j][e]) * sc[j][e] + sh[j][e];
-                    if (p.fuse_silu) yv = silu_f(yv);
-                    o[e] = (half_t)yv;
-                }
+                GN_NORM8(LO, v[u][j], w[u][j], lcol[j].m, sc[j], sh[j], p.fuse_silu, o)
                 if (r < r_end && cc < CH) {                      // ... only the stores are conditional
                     st8(p.y + off + cc * 8, o);
                     if (p.xcopy) st8(p.xcopy + off + cc * 8, v[u][j]);      // the concatenated input, once, for the shortcut / backward
@@ -582,6 +626,7 @@ __device__ __forceinline__ void gn_res_reduce(float* red, float* chs, const floa
     __syncthreads();
 }
 
+// A thread's rows are rl + k * nrl, k < NPT, of the window [0, HW): the first npt = cdiv(HW, nrl) slots are loaded, the others are zero.
 // DEF: x is a deferred split-K GEMM (GnArgs.fin_*): every chunk is folded from the slabs with the GEMM's own epilogue while it is
 // loaded (finish_chunk8: the bits the finish kernel would have stored) and written back once through xcopy.
 // LO (never with DEF): the rows' remainders stay in registers next to the rows
@@ -638,23 +683,13 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = k < npt && rl + k * nrl < p.HW;
-            if constexpr (LO) {
-                float xv[8];
-                gn_val8(v[k], w[k], lcol.m, xv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
-            } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
-            }
+            GN_ACCUM8(LO, v[k], w[k], lcol.m, piv, ok, s, q)
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f / ((float)p.HW * (float)cpg));
-    if (t < gps) {                                               // (E[x - P], E[(x - P)^2]) -> (mean, rstd)
-        const float dm = mr[t * 2], mean = pv[t] + dm;
-        float var = mr[t * 2 + 1] - dm * dm;
-        var = var < 0.f ? 0.f : var;
-        const float rstd = rsqrtf(var + p.eps);
+    if (t < gps) {
+        float mean, rstd;
+        gn_stats_from_moments(mr[t * 2], mr[t * 2 + 1], pv[t], p.eps, mean, rstd);
         mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         float* st = p.stats + ((size_t)b * p.G + blockIdx.y * gps + t) * 2;
@@ -662,26 +697,16 @@ __global__ __launch_bounds__(NT) void gn_fwd_resident_kernel(GnArgs p) {
     }
     __syncthreads();
     if (!active) return;
-    float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int cl = c0 * 8 + e, g = cl / cpg;
-        sc[e] = mr[g * 2 + 1] * (e < 4 ? ga[e & 3] : gb[e & 3]);
-        sh[e] = (e < 4 ? ba[e & 3] : bb[e & 3]) - mr[g * 2] * sc[e];
-    }
+    float sc[8], sh[8], gam[8], bet[8];
+    gn_unpack8(ga, gb, gam);
+    gn_unpack8(ba, bb, bet);
+    gn_affine8(mr, c0 * 8, cpg, gam, bet, sc, sh);
     half_t* ybase = p.y + (size_t)b * p.HW * p.C + cb + c0 * 8;
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const int r = rl + k * nrl;
-        float xv[8];
-        if constexpr (LO) gn_val8(v[k], w[k], lcol.m, xv);
         half8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float yv = (LO ? xv[e] : (float)v[k][e]) * sc[e] + sh[e];
-            if (p.fuse_silu) yv = silu_f(yv);
-            o[e] = (half_t)yv;
-        }
+        GN_NORM8(LO, v[k], w[k], lcol.m, sc, sh, p.fuse_silu, o)
         if (k < npt && r < p.HW) {
             st8(ybase + (size_t)r * p.C, o);
             if (p.xcopy) st8(p.xcopy + (size_t)b * p.HW * p.C + cb + c0 * 8 + (size_t)r * p.C, v[k]);
@@ -829,6 +854,8 @@ __device__ __forceinline__ bool gn_team_exchange(const GnArgs& p, int u, int m, 
     return true;
 }
 
+// Member m's rows are r0 + rl + k * nrl, k < NPT, of the window [r0, r_end) = its tm_rpb rows; every slot is loaded, rows past the
+// window clamped to r0.  Apart from the window, the loads and the exchange these are the resident kernels.
 template <int NT, int NPT, bool LO = false>
 __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
     __shared__ float red[NT * 16];
@@ -868,24 +895,14 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             const bool ok = r0 + rl + k * nrl < r_end;
-            if constexpr (LO) {
-                float xv[8];
-                gn_val8(v[k], w[k], lcol.m, xv);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { const float f = ok ? xv[e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
-            } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { const float f = ok ? (float)v[k][e] - piv[e] : 0.f; s[e] += f; q[e] += f * f; }
-            }
+            GN_ACCUM8(LO, v[k], w[k], lcol.m, piv, ok, s, q)
         }
     }
     gn_res_reduce<NT>(red, chs, s, q, t, p.CS, cpg, gps, rl, nrl, c0, active, nullptr, mr, 1.0f);
     if (!gn_team_exchange<NT>(p, u, m, s_epoch, gps * 2, mr, gat, 1.0f / ((float)p.HW * (float)cpg))) return;
-    if (t < gps) {                                               // (E[x - P], E[(x - P)^2]) -> (mean, rstd)
-        const float dm = mr[t * 2], mean = gn_pivot(p, b, cb + t * cpg) + dm;
-        float var = mr[t * 2 + 1] - dm * dm;
-        var = var < 0.f ? 0.f : var;
-        const float rstd = rsqrtf(var + p.eps);
+    if (t < gps) {
+        float mean, rstd;
+        gn_stats_from_moments(mr[t * 2], mr[t * 2 + 1], gn_pivot(p, b, cb + t * cpg), p.eps, mean, rstd);
         mr[t * 2] = mean;
         mr[t * 2 + 1] = rstd;
         if (m == 0) {
@@ -895,26 +912,16 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
     }
     __syncthreads();
     if (!active) return;
-    float sc[8], sh[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int cl = c0 * 8 + e, g = cl / cpg;
-        sc[e] = mr[g * 2 + 1] * (e < 4 ? ga[e & 3] : gb[e & 3]);
-        sh[e] = (e < 4 ? ba[e & 3] : bb[e & 3]) - mr[g * 2] * sc[e];
-    }
+    float sc[8], sh[8], gam[8], bet[8];
+    gn_unpack8(ga, gb, gam);
+    gn_unpack8(ba, bb, bet);
+    gn_affine8(mr, c0 * 8, cpg, gam, bet, sc, sh);
     half_t* ybase = p.y + (size_t)b * p.HW * p.C + cb + c0 * 8;
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
         const int r = r0 + rl + k * nrl;
-        float xv[8];
-        if constexpr (LO) gn_val8(v[k], w[k], lcol.m, xv);
         half8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float yv = (LO ? xv[e] : (float)v[k][e]) * sc[e] + sh[e];
-            if (p.fuse_silu) yv = silu_f(yv);
-            o[e] = (half_t)yv;
-        }
+        GN_NORM8(LO, v[k], w[k], lcol.m, sc, sh, p.fuse_silu, o)
         if (r < r_end) {
             st8(ybase + (size_t)r * p.C, o);
             if (p.xcopy) st8(p.xcopy + (size_t)b * p.HW * p.C + cb + c0 * 8 + (size_t)r * p.C, v[k]);
@@ -922,6 +929,10 @@ __global__ __launch_bounds__(NT) void gn_fwd_team_kernel(GnArgs p) {
     }
 }
 
+// The backward kernels (partial, apply2, resident, team) keep their bodies written out: the text of gn_bwd_resident_kernel on the
+// member's window.  Shared per-chunk functions (coefficients, accumulate, k2 / k3, dx store) were byte-equal but measured slower on the
+// dres path: 0.4 - 1.1 % in this kernel, 0.65 - 0.8 % in gn_bwd_resident_kernel<256, 4>, against a run-to-run spread of 0.04 - 0.6 %
+// (profiles/norm_refactor_ab.txt); with only some of them shared, the fused / unfused multiply-add mix, and so the bits, changed.
 template <int NT, int NPT>
 __global__ __launch_bounds__(NT) void gn_bwd_team_kernel(GnArgs p) {
     __shared__ float red[NT * 16];
@@ -1307,9 +1318,12 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const half_t* x, half
     }
 }
 
-int gn_plan(GnArgs& a, void* ws, size_t ws_bytes, bool bwd, bool params) {
-    if (a.B <= 0 || a.HW <= 0 || a.C <= 0 || a.G <= 0 || a.G > 64 || (a.C % a.G) || (a.C & 7) || a.C > 4096)
-        return CLORA_ERR_ARG;
+bool gn_shape_ok(int B, int HW, int C, int G) {
+    return !(B <= 0 || HW <= 0 || C <= 0 || G <= 0 || G > 64 || (C % G) || (C & 7) || C > 4096);
+}
+
+// Two-launch form: row chunks and channel slabs of the (nchunk, nslab, B) grid
+void gn_plan(GnArgs& a) {
     const int CH = a.C / 8;
     const int nrl = CH >= 256 ? 1 : 256 / CH;
     const long kBlocks = clora_option(CLORA_OPT_GN_BLOCKS);
@@ -1338,9 +1352,15 @@ int gn_plan(GnArgs& a, void* ws, size_t ws_bytes, bool bwd, bool params) {
         a.nslab = nslab;
         a.CS = a.C / nslab;
     }
+}
+// ... and its workspace: the group partials, then (trainable affine) the channel partials
+size_t gn_workspace_bytes(const GnArgs& a, bool params) {
     size_t need = (size_t)a.B * a.nchunk * a.G * 2;
     if (params) need += (size_t)a.B * a.nchunk * a.C * 2;
-    if (!ws || ws_bytes < need * sizeof(float)) return CLORA_ERR_WORKSPACE;
+    return need * sizeof(float);
+}
+int gn_bind_workspace(GnArgs& a, void* ws, size_t ws_bytes, bool params) {
+    if (!ws || ws_bytes < gn_workspace_bytes(a, params)) return CLORA_ERR_WORKSPACE;
     a.partial = (float*)ws;
     a.chpart = params ? a.partial + (size_t)a.B * a.nchunk * a.G * 2 : nullptr;
     return CLORA_OK;
@@ -1417,6 +1437,91 @@ int gn_team_plan(GnArgs& a, bool bwd, bool params, void* state, size_t state_byt
     return pick_npt <= 4 ? 4 : (pick_npt <= 8 ? 8 : 16);
 }
 
+// ---- which form runs, for both directions
+enum GnForm { kGnTwoLaunch, kGnResident, kGnTeam };
+struct GnLaunchPlan {
+    GnForm form;
+    int nt, npt;          // resident / team: threads per block and rows per thread of the instantiation
+    int nj, uf;           // two-launch: column chunks per thread and load-batch factor of the instantiation
+    bool deferred_here;   // the launch folds the deferred split-K producer of its input; else the caller finishes it first
+};
+// Fills in the geometry of the chosen form in `a` (slabs, chunks, the team's exchange state).  `deferred`: the input (forward: x,
+// backward: dy) is an unfinished split-K GEMM.
+// Host-only and launch-free: the caller runs clora_finish_deferred AFTER this returns, where it used to run between the resident and
+// the team planner.  So gn_team_plan (whose first call asks the device for its CU count) now precedes the finish, and when the finish
+// fails `a` already points at the team state -- the caller returns the error and launches nothing, `a` is a local of the call.
+GnLaunchPlan gn_launch_plan(GnArgs& a, bool bwd, bool params, bool deferred, void* team_state, size_t team_state_bytes) {
+    GnLaunchPlan pl = {kGnTwoLaunch, 0, 0, 1, 1, false};
+    const GnResident res = gn_resident_plan(a, bwd, params);
+    // Folding pays only where a thread owns few rows (npt <= 4: the 8x8 / 16x16 maps): the one-launch kernels run 32-128 blocks and a
+    // thread's rows are folded one after the other -- measured on MI355X (profiles/r06_deferred_ab.txt): 9.6 us against 6.6 + 6.0 for
+    // finish + plain at npt 4, but 17.4 against 8.1 + 6.0 at npt 8 and 36.2 against 13.9 + 6.0 at npt 16.  Everything else: the
+    // plain finish pass (2048 blocks) first, then the plain passes over the finished tensor.
+    const bool fold_shape = res.nt && res.npt <= clora_option(CLORA_OPT_DEFER_MAX_ROWS);
+    pl.deferred_here = deferred && fold_shape;
+    // large maps: one launch, a team per unit.  Shapes whose one-block-per-slab plan can fold a deferred producer keep that plan whether
+    // or not this call's input is deferred (deferring never changes the bits)
+    if (!fold_shape && (!res.nt || clora_option(CLORA_OPT_GN_TEAM) >= 2)) {
+        GnArgs ta = a;
+        const int npt = gn_team_plan(ta, bwd, params, team_state, team_state_bytes);
+        if (npt) {
+            a = ta;
+            pl.form = kGnTeam; pl.nt = kTeamNT; pl.npt = npt;
+            return pl;
+        }
+    }
+    if (res.nt) {
+        pl.form = kGnResident; pl.nt = res.nt; pl.npt = res.npt;
+        return pl;
+    }
+    gn_plan(a);
+    pl.nj = a.CS / 8 > 256 ? 2 : 1;                                             // slabs wider than 2048 channels: two column chunks per thread
+    pl.uf = (pl.nj == 1 && clora_option(CLORA_OPT_GN_UNROLL)) ? 2 : 1;          // twice the rows in flight per thread (same accumulation order: same bits)
+    return pl;
+}
+
+// ---- plan -> instantiation, one dispatcher per form
+// One block per (slab, batch element).  The backward keeps x and dy in registers, so it has no 16-row instantiation, and it recomputes
+// from x, so it has no LO one.
+template <bool BWD, bool DEF, bool LO>
+void gn_resident_launch(const GnArgs& a, int nt, int npt, hipStream_t s) {
+    static_assert(!(BWD && LO) && !(DEF && LO), "no such instantiation");
+    const dim3 grid(1, a.nslab, a.B);
+    if constexpr (BWD) {
+        if (nt == 256 && npt == 4) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 4, DEF>), grid, dim3(256), 0, s, a);
+        else if (nt == 256) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 8, DEF>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((gn_bwd_resident_kernel<512, 8, DEF>), grid, dim3(512), 0, s, a);
+    } else {
+        if (nt == 256 && npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4, DEF, LO>), grid, dim3(256), 0, s, a);
+        else if (nt == 256 && npt == 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 8, DEF, LO>), grid, dim3(256), 0, s, a);
+        else if (nt == 256) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 16, DEF, LO>), grid, dim3(256), 0, s, a);
+        else if (npt <= 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 8, DEF, LO>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 16, DEF, LO>), grid, dim3(512), 0, s, a);
+    }
+}
+
+// partial -> (backward, trainable affine: the parameter fold, inside the apply launch when it has enough blocks) -> apply
+template <bool BWD, bool LO, int NJ, int UF>
+void gn_two_launch_as(GnArgs& a, hipStream_t s) {
+    const dim3 grid(a.nchunk, a.nslab, a.B), block(256);
+    if constexpr (BWD) {
+        static_assert(!LO, "no such instantiation");
+        hipLaunchKernelGGL((gn_bwd_partial_kernel<NJ, UF>), grid, block, 0, s, a);
+        a.params_in_apply = (a.dgamma && (long)a.nchunk * a.nslab * a.B >= clora_cdiv(a.C, 32)) ? 1 : 0;
+        if (a.dgamma && !a.params_in_apply) hipLaunchKernelGGL(gn_bwd_params_kernel, dim3(clora_cdiv(a.C, 32)), block, 0, s, a);
+        hipLaunchKernelGGL((gn_bwd_apply2_kernel<NJ, UF>), grid, block, 0, s, a);
+    } else {
+        hipLaunchKernelGGL((gn_fwd_partial_kernel<NJ, UF, LO>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((gn_fwd_apply2_kernel<NJ, UF, LO>), grid, block, 0, s, a);
+    }
+}
+template <bool BWD, bool LO>
+void gn_two_launch(GnArgs& a, int nj, int uf, hipStream_t s) {
+    if (nj == 2) gn_two_launch_as<BWD, LO, 2, 1>(a, s);
+    else if (uf == 2) gn_two_launch_as<BWD, LO, 1, 2>(a, s);
+    else gn_two_launch_as<BWD, LO, 1, 1>(a, s);
+}
+
 template <bool BWD, bool LO = false>
 void gn_team_launch(GnArgs& a, int npt, hipStream_t s) {
     const dim3 grid(kTeamBlocks), block(kTeamNT);
@@ -1441,13 +1546,12 @@ int ew_blocks(size_t n) {
 }  // namespace
 
 extern "C" size_t clora_groupnorm_workspace_bytes(int B, int HW, int C, int G, int backward, int param_grads) {
+    (void)backward;                                              // the two-launch geometry is that of the forward
+    if (!gn_shape_ok(B, HW, C, G)) return 0;
     GnArgs a = GnArgs();
     a.B = B; a.HW = HW; a.C = C; a.G = G;
-    static float dummy;
-    if (gn_plan(a, &dummy, (size_t)-1, backward != 0, param_grads != 0) != CLORA_OK) return 0;
-    size_t need = (size_t)B * a.nchunk * G * 2;
-    if (param_grads) need += (size_t)B * a.nchunk * C * 2;
-    return need * sizeof(float);
+    gn_plan(a);
+    return gn_workspace_bytes(a, param_grads != 0);
 }
 
 namespace {
@@ -1466,7 +1570,7 @@ int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_d
     if (!x2) x2_lo = nullptr;                                    // the remainder of a half that is not there
     const bool lo = x_lo || x2_lo;                               // the plans are those of the plain call; only the instantiations differ
     if (lo && src && src->splits > 0) return CLORA_ERR_ARG;      // a launch that writes a remainder is never deferred
-    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || G > 64 || (C % G) || (C & 7) || C > 4096) return CLORA_ERR_ARG;
+    if (!gn_shape_ok(B, HW, C, G)) return CLORA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const bool deferred = src && src->splits > 0;
     if (deferred) {
@@ -1479,81 +1583,28 @@ int gn_fwd_impl(const clora_half* x, const clora_half* x2, int Ca, const clora_d
     a.B = B; a.HW = HW; a.C = C; a.G = G; a.eps = eps; a.fuse_silu = fuse_silu;
     a.x2 = (const half_t*)x2; a.Ca = x2 ? Ca : C; a.xcopy = (half_t*)xcopy;
     a.x_lo = (const half_t*)x_lo; a.x2_lo = (const half_t*)x2_lo;
-    const GnResident res = gn_resident_plan(a, false, false);
-    // Folding pays only where a thread owns few rows (npt <= 4: the 8x8 / 16x16 maps): the one-launch kernels run 32-128 blocks and a
-    // thread's rows are folded one after the other -- measured on MI355X (profiles/r06_deferred_ab.txt): 9.6 us against 6.6 + 6.0 for
-    // finish + plain at npt 4, but 17.4 against 8.1 + 6.0 at npt 8 and 36.2 against 13.9 + 6.0 at npt 16.  Everything else: the
-    // plain finish pass (2048 blocks) first.
-    bool deferred_here = deferred && res.nt && res.npt <= clora_option(CLORA_OPT_DEFER_MAX_ROWS);
-    if (deferred && !deferred_here) {                            // finish first, then the plain passes over src->C
+    const GnLaunchPlan pl = gn_launch_plan(a, false, false, deferred, team_state, team_state_bytes);
+    if (deferred && !pl.deferred_here) {
         const int rc = clora_finish_deferred(src, stream);
         if (rc != CLORA_OK) return rc;
     }
-    // large maps: one launch, a team per unit.  Shapes whose one-block-per-slab plan can fold a deferred producer keep that plan whether
-    // or not this call's input is deferred (deferring never changes the bits)
-    const bool fold_shape = res.nt && res.npt <= clora_option(CLORA_OPT_DEFER_MAX_ROWS);
-    if (!fold_shape && (!res.nt || clora_option(CLORA_OPT_GN_TEAM) >= 2)) {
-        GnArgs ta = a;
-        const int npt = gn_team_plan(ta, false, false, team_state, team_state_bytes);
-        if (npt) {
-            if (lo) gn_team_launch<false, true>(ta, npt, s);
-            else gn_team_launch<false>(ta, npt, s);
-            return clora_check_launch();
-        }
-    }
-    if (res.nt) {
-        const dim3 rgrid(1, a.nslab, B);
-        if (lo) {
-            if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4, false, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.nt == 256 && res.npt == 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 8, false, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.nt == 256) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 16, false, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.npt <= 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 8, false, true>), rgrid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 16, false, true>), rgrid, dim3(512), 0, s, a);
-            return clora_check_launch();
-        }
-        if (deferred_here) {
+    if (pl.form == kGnTeam) {
+        if (lo) gn_team_launch<false, true>(a, pl.npt, s);
+        else gn_team_launch<false>(a, pl.npt, s);
+    } else if (pl.form == kGnResident) {
+        if (pl.deferred_here) {                                  // (never with lo, see above) the finished x is written back through xcopy
             a.fin_partial = src->partial; a.fin_splits = src->splits; a.fin_epi = src->epi; a.xcopy = (half_t*)src->C;
-            if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.nt == 256 && res.npt == 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 8, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.nt == 256) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 16, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.npt <= 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 8, true>), rgrid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 16, true>), rgrid, dim3(512), 0, s, a);
-            return clora_check_launch();
-        }
-        if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 4>), rgrid, dim3(256), 0, s, a);
-        else if (res.nt == 256 && res.npt == 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 8>), rgrid, dim3(256), 0, s, a);
-        else if (res.nt == 256) hipLaunchKernelGGL((gn_fwd_resident_kernel<256, 16>), rgrid, dim3(256), 0, s, a);
-        else if (res.npt <= 8) hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 8>), rgrid, dim3(512), 0, s, a);
-        else hipLaunchKernelGGL((gn_fwd_resident_kernel<512, 16>), rgrid, dim3(512), 0, s, a);
-        return clora_check_launch();
-    }
-    int rc = gn_plan(a, workspace, workspace_bytes, false, false);
-    if (rc != CLORA_OK) return rc;
-    const dim3 grid(a.nchunk, a.nslab, B);
-    if (lo) {                                                    // the same three forms as below
-        if (a.CS / 8 > 256) {
-            hipLaunchKernelGGL((gn_fwd_partial_kernel<2, 1, true>), grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL((gn_fwd_apply2_kernel<2, 1, true>), grid, dim3(256), 0, s, a);
-        } else if (clora_option(CLORA_OPT_GN_UNROLL)) {
-            hipLaunchKernelGGL((gn_fwd_partial_kernel<1, 2, true>), grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL((gn_fwd_apply2_kernel<1, 2, true>), grid, dim3(256), 0, s, a);
+            gn_resident_launch<false, true, false>(a, pl.nt, pl.npt, s);
+        } else if (lo) {
+            gn_resident_launch<false, false, true>(a, pl.nt, pl.npt, s);
         } else {
-            hipLaunchKernelGGL((gn_fwd_partial_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL((gn_fwd_apply2_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
+            gn_resident_launch<false, false, false>(a, pl.nt, pl.npt, s);
         }
-        return clora_check_launch();
-    }
-    if (a.CS / 8 > 256) {                                        // slabs wider than 2048 channels: two column chunks per thread
-        hipLaunchKernelGGL(gn_fwd_partial_kernel<2>, grid, dim3(256), 0, s, a);
-        hipLaunchKernelGGL(gn_fwd_apply2_kernel<2>, grid, dim3(256), 0, s, a);
     } else {
-        if (clora_option(CLORA_OPT_GN_UNROLL)) {                 // twice the rows in flight per thread (same accumulation order: same bits)
-            hipLaunchKernelGGL((gn_fwd_partial_kernel<1, 2>), grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL((gn_fwd_apply2_kernel<1, 2>), grid, dim3(256), 0, s, a);
-        } else {
-            hipLaunchKernelGGL(gn_fwd_partial_kernel<1>, grid, dim3(256), 0, s, a);
-            hipLaunchKernelGGL(gn_fwd_apply2_kernel<1>, grid, dim3(256), 0, s, a);
-        }
+        const int rc = gn_bind_workspace(a, workspace, workspace_bytes, false);
+        if (rc != CLORA_OK) return rc;
+        if (lo) gn_two_launch<false, true>(a, pl.nj, pl.uf, s);
+        else gn_two_launch<false, false>(a, pl.nj, pl.uf, s);
     }
     return clora_check_launch();
 }
@@ -1596,7 +1647,7 @@ int gn_bwd_impl(const clora_half* x, const clora_half* dy, const clora_deferred_
                 const float* stats, float* dgamma, float* dbeta, int B, int HW, int C, int G, int fuse_silu,
                 int accumulate_params, void* team_state, size_t team_state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     if (!x || !dx || !gamma || !beta || !stats || ((dgamma == nullptr) != (dbeta == nullptr))) return CLORA_ERR_ARG;
-    if (B <= 0 || HW <= 0 || C <= 0 || G <= 0 || G > 64 || (C % G) || (C & 7) || C > 4096) return CLORA_ERR_ARG;
+    if (!gn_shape_ok(B, HW, C, G)) return CLORA_ERR_ARG;
     if (dx2 && (Ca <= 0 || Ca >= C || (Ca & 7))) return CLORA_ERR_ARG;
     const bool deferred = dy_src && dy_src->splits > 0;
     if (deferred) {
@@ -1610,47 +1661,26 @@ int gn_bwd_impl(const clora_half* x, const clora_half* dy, const clora_deferred_
     a.B = B; a.HW = HW; a.C = C; a.G = G; a.fuse_silu = fuse_silu; a.accumulate_params = accumulate_params;
     a.y2 = (half_t*)dx2; a.Ca = dx2 ? Ca : C;
     hipStream_t s = (hipStream_t)stream;
-    const GnResident res = gn_resident_plan(a, true, dgamma != nullptr);
-    const bool deferred_here = deferred && res.nt && res.npt <= clora_option(CLORA_OPT_DEFER_MAX_ROWS);      // see the forward
-    if (deferred && !deferred_here) {
+    const bool params = dgamma != nullptr;
+    const GnLaunchPlan pl = gn_launch_plan(a, true, params, deferred, team_state, team_state_bytes);
+    if (deferred && !pl.deferred_here) {
         const int rc = clora_finish_deferred(dy_src, stream);
         if (rc != CLORA_OK) return rc;
     }
-    const bool fold_shape = res.nt && res.npt <= clora_option(CLORA_OPT_DEFER_MAX_ROWS);      // see the forward
-    if (!fold_shape && (!res.nt || clora_option(CLORA_OPT_GN_TEAM) >= 2)) {
-        GnArgs ta = a;
-        const int npt = gn_team_plan(ta, true, dgamma != nullptr, team_state, team_state_bytes);
-        if (npt) {
-            gn_team_launch<true>(ta, npt, s);
-            return clora_check_launch();
-        }
-    }
-    if (res.nt) {
-        const dim3 rgrid(1, a.nslab, B);
-        if (deferred_here) {
+    if (pl.form == kGnTeam) {
+        gn_team_launch<true>(a, pl.npt, s);
+    } else if (pl.form == kGnResident) {
+        if (pl.deferred_here) {
             a.fin_partial = dy_src->partial; a.fin_splits = dy_src->splits; a.fin_epi = dy_src->epi;
-            if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 4, true>), rgrid, dim3(256), 0, s, a);
-            else if (res.nt == 256) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 8, true>), rgrid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((gn_bwd_resident_kernel<512, 8, true>), rgrid, dim3(512), 0, s, a);
-            return clora_check_launch();
+            gn_resident_launch<true, true, false>(a, pl.nt, pl.npt, s);
+        } else {
+            gn_resident_launch<true, false, false>(a, pl.nt, pl.npt, s);
         }
-        if (res.nt == 256 && res.npt == 4) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 4>), rgrid, dim3(256), 0, s, a);
-        else if (res.nt == 256) hipLaunchKernelGGL((gn_bwd_resident_kernel<256, 8>), rgrid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((gn_bwd_resident_kernel<512, 8>), rgrid, dim3(512), 0, s, a);
-        return clora_check_launch();
+    } else {
+        const int rc = gn_bind_workspace(a, workspace, workspace_bytes, params);
+        if (rc != CLORA_OK) return rc;
+        gn_two_launch<true, false>(a, pl.nj, pl.uf, s);
     }
-    int rc = gn_plan(a, workspace, workspace_bytes, true, dgamma != nullptr);
-    if (rc != CLORA_OK) return rc;
-    const dim3 grid(a.nchunk, a.nslab, B);
-    const bool two = a.CS / 8 > 256;                             // slabs wider than 2048 channels
-    if (two) hipLaunchKernelGGL(gn_bwd_partial_kernel<2>, grid, dim3(256), 0, s, a);
-    else if (clora_option(CLORA_OPT_GN_UNROLL)) hipLaunchKernelGGL((gn_bwd_partial_kernel<1, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(gn_bwd_partial_kernel<1>, grid, dim3(256), 0, s, a);
-    a.params_in_apply = (dgamma && (long)a.nchunk * a.nslab * B >= clora_cdiv(C, 32)) ? 1 : 0;
-    if (dgamma && !a.params_in_apply) hipLaunchKernelGGL(gn_bwd_params_kernel, dim3(clora_cdiv(C, 32)), dim3(256), 0, s, a);
-    if (two) hipLaunchKernelGGL(gn_bwd_apply2_kernel<2>, grid, dim3(256), 0, s, a);
-    else if (clora_option(CLORA_OPT_GN_UNROLL)) hipLaunchKernelGGL((gn_bwd_apply2_kernel<1, 2>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(gn_bwd_apply2_kernel<1>, grid, dim3(256), 0, s, a);
     return clora_check_launch();
 }
 }  // namespace
@@ -1680,23 +1710,27 @@ extern "C" int clora_groupnorm_bwd_f16(const clora_half* x, const clora_half* dy
                                       accumulate_params, workspace, workspace_bytes, stream);
 }
 
-extern "C" int clora_layernorm_fwd_f16(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M,
-                                       int C, float eps, void* stream) {
+namespace {
+// x_lo == nullptr: the plain kernels
+int ln_fwd_impl(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M, int C, float eps,
+                const clora_half* x_lo, void* stream) {
     if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || (C & 7) || C / 8 > 64 * kLnCols) return CLORA_ERR_ARG;
     LnArgs a = LnArgs();
-    a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.M = M; a.C = C; a.eps = eps;
-    launch_layernorm<false>(a, (hipStream_t)stream);
+    a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.M = M; a.C = C; a.eps = eps; a.x_lo = (const half_t*)x_lo;
+    if (x_lo) launch_layernorm<false, false, true>(a, (hipStream_t)stream);
+    else launch_layernorm<false>(a, (hipStream_t)stream);
     return clora_check_launch();
+}
+}  // namespace
+
+extern "C" int clora_layernorm_fwd_f16(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M,
+                                       int C, float eps, void* stream) {
+    return ln_fwd_impl(x, y, gamma, beta, M, C, eps, nullptr, stream);
 }
 
 extern "C" int clora_layernorm_fwd_f16_lo(const clora_half* x, clora_half* y, const float* gamma, const float* beta, int M,
                                           int C, float eps, const clora_half* x_lo, void* stream) {
-    if (!x_lo) return clora_layernorm_fwd_f16(x, y, gamma, beta, M, C, eps, stream);
-    if (!x || !y || !gamma || !beta || M <= 0 || C <= 0 || (C & 7) || C / 8 > 64 * kLnCols) return CLORA_ERR_ARG;
-    LnArgs a = LnArgs();
-    a.x = (const half_t*)x; a.y = (half_t*)y; a.gamma = gamma; a.beta = beta; a.M = M; a.C = C; a.eps = eps; a.x_lo = (const half_t*)x_lo;
-    launch_layernorm<false, false, true>(a, (hipStream_t)stream);
-    return clora_check_launch();
+    return ln_fwd_impl(x, y, gamma, beta, M, C, eps, x_lo, stream);
 }
 
 extern "C" int clora_layernorm_bwd_f16_ex(const clora_half* x, const clora_half* dy, const clora_deferred_t* dy_src, const clora_half* dres,

@@ -933,6 +933,78 @@ def _case_deferred_finish(dev, B, HW, C, Kd, G, split, silu=True, seed=12, lora=
     assert not K._PENDING and torch.equal(dyd, ref) and torch.equal(z, K.add(ref, ref))
 
 
+# GroupNorm instantiations that no other GPU case reaches (profiles/norm_refactor_bits.txt lists which case reaches which): the smallest
+# shape that gn_resident_plan / gn_team_plan / gn_plan (clora_norm.hip) route there, with the knobs that take it there.
+#   (what, B, HW, C, G, knobs, lo, deferred)
+GN_INSTANTIATION_CASES = [
+    # one group of 4096 channels: a slab wider than 2048, two column chunks per thread -- gn_fwd_partial / apply2<2, 1, false> and
+    # <2, 1, true>, gn_bwd_partial / apply2<2, 1> with and without the channel partials
+    ("two_launch_nj2", 1, 16, 4096, 1, {}, False, False),
+    ("two_launch_nj2_lo", 1, 16, 4096, 1, {}, True, False),
+    # gn_fwd_partial / apply2<1, 2, true>: the remainder under "gn_unroll"
+    ("two_launch_unroll_lo", 1, 64, 320, 32, dict(gn_resident=0, gn_unroll=1), True, False),
+    # a 320-channel slab (two groups of 320) does not fit 256 threads: 512 threads, 12 row lanes, 6 rows per thread --
+    # gn_fwd_resident_kernel<512, 8> plain, with the remainder and folding a deferred producer
+    ("resident_512_8", 1, 64, 640, 2, {}, False, False),
+    ("resident_512_8_lo", 1, 64, 640, 2, {}, True, False),
+    ("resident_512_8_def", 1, 64, 640, 2, dict(defer_max_rows=16), False, True),
+    # 64-channel slab, 400 rows: 13 rows per thread at 256 threads forward (gn_fwd_resident_kernel<256, 16, true>), 7 at 512 threads
+    # backward (gn_bwd_resident_kernel<512, 8, true>), both folding the deferred producer
+    ("resident_400_rows_def", 1, 400, 64, 8, dict(defer_max_rows=16), False, True),
+]
+
+
+def case_groupnorm_instantiation(dev, B, HW, C, G, knobs, lo, deferred, eps=1e-5, seed=17):
+    """forward (8e-4), dx with dres (2e-3) and, through the trainable-affine call, dgamma / dbeta (1e-3) against fp32 torch -- the limits
+    of case_groupnorm -- and a second launch of each giving the bits of the first.  lo: the input is hi + lo (clora_groupnorm_fwd_f16_lo);
+    deferred: the forward's x and the backward's dy are unfinished split-K GEMMs (bias + row add + residual) that the norm folds."""
+    g = torch.Generator().manual_seed(seed)
+    M, Kd = B * HW, 128
+    gamma, beta = (1 + 0.2 * rnd((C,), dev, g, dtype=f32)), 0.2 * rnd((C,), dev, g, dtype=f32)
+    x_lo = rnd((B, HW, C), dev, g, 1e-3) if lo else None
+    dy, dres = rnd((B, HW, C), dev, g), rnd((B, HW, C), dev, g)
+    A, Wt = rnd((M, Kd), dev, g), rnd((C, Kd), dev, g, 0.1)
+    kw = dict(bias=rnd((C,), dev, g, dtype=f32), residual=rnd((M, C), dev, g), rowadd=rnd((B, C), dev, g), rows_per_batch=HW, split_k=2)
+    assert not K._PENDING
+    x = K.gemm(A, Wt, M, C, Kd, **kw).reshape(B, HW, C) if deferred else (rnd((B, HW, C), dev, g).float() * 1.5 + 0.3).half()
+    producer = lambda: K.gemm(A, Wt, M, C, Kd, defer=True, **kw).reshape(B, HW, C)
+    x32 = (x.float() + (x_lo.float() if lo else 0)).clone().requires_grad_(True)
+    g32, b32 = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    y = F.silu(F.group_norm(x32.permute(0, 2, 1), G, g32, b32, eps).permute(0, 2, 1))
+    rows = knobs.get("defer_max_rows")
+    rest = {k_: v_ for k_, v_ in knobs.items() if k_ != "defer_max_rows"}
+    if rows is not None:
+        K.set_option("defer_max_rows", rows)
+    try:
+        with options(**rest):
+            fwd = lambda: K.groupnorm_fwd(producer() if deferred else x, gamma, beta, G, eps, True, x_lo=x_lo)
+            out, stats = fwd()
+            out1, stats1 = fwd()
+            assert not K._PENDING and torch.equal(out1, out) and torch.equal(stats1, stats)
+            e_y = rel(out, y.detach())
+            print(f"GN_INSTANTIATION {(B, HW, C, G)} {knobs} lo={lo} deferred={deferred} y={e_y:.2e}")
+            assert e_y < 8e-4
+            if lo:
+                return                                           # the backward recomputes from x alone: no remainder form
+            # the backward: dy = the deferred tensor where there is one (the same values as x: any fp16 tensor serves as a gradient)
+            gy = x if deferred else dy
+            y.backward(gy.float())
+            bwd = lambda **kw_: K.groupnorm_bwd(x, producer() if deferred else gy, gamma, beta, stats, G, True, **kw_)
+            dx, _, _ = bwd(dres=dres)
+            dx1, _, _ = bwd(dres=dres)
+            assert not K._PENDING and torch.equal(dx1, dx)
+            dxp, dg, db = bwd(want_param_grads=True)
+            dxp1, dg1, db1 = bwd(want_param_grads=True)
+            assert torch.equal(dxp1, dxp) and torch.equal(dg1, dg) and torch.equal(db1, db)
+            errs = dict(dx=rel(dx, x32.grad + dres.float()), dx_params=rel(dxp, x32.grad), dgamma=rel(dg, g32.grad), dbeta=rel(db, b32.grad))
+            print(f"GN_INSTANTIATION {(B, HW, C, G)} {knobs} deferred={deferred} " + " ".join(f"{k_}={v_:.2e}" for k_, v_ in errs.items()))
+            assert errs["dx"] < 2e-3 and errs["dx_params"] < 2e-3 and errs["dgamma"] < 1e-3 and errs["dbeta"] < 1e-3, errs
+    finally:
+        if rows is not None:
+            K.set_option("defer_max_rows", int(os.environ.get("CLORA_DEFER_MAX_ROWS", "4")))
+    assert K.gn_team_errors(x.device) == 0
+
+
 def case_gemm_fused_layernorm(dev, M, Kd, tile_cfg, seed=13, lora=False, residual=True):
     """Round 6 (clora_epilogue_t.ln_out): the LayerNorm that follows a projection, written by the projection's own launch where one
     320-column tile spans the row, == clora_layernorm_fwd_f16 on the stored output (same partition / formulas / summation order: the

@@ -287,6 +287,11 @@ def test_groupnorm(B, HW, C, G, silu, train):
     KC.case_groupnorm("cpu", B, HW, C, G, silu, train_params=train)
 
 
+@pytest.mark.parametrize("what,B,HW,C,G,knobs,lo,deferred", KC.GN_INSTANTIATION_CASES, ids=[c[0] for c in KC.GN_INSTANTIATION_CASES])
+def test_groupnorm_instantiations_no_other_case_reaches(what, B, HW, C, G, knobs, lo, deferred):
+    KC.case_groupnorm_instantiation("cpu", B, HW, C, G, knobs, lo, deferred)
+
+
 def test_groupnorm_random_shapes():
     """seeded sweep over group sizes 1..80 channels, 1..513 rows, 1..32 groups: whichever plan a shape gets (one launch, two launches,
     channel slabs, two column chunks per thread) agrees with torch, with the other plan and with itself (case_groupnorm)"""

@@ -217,6 +217,13 @@ def test_groupnorm(B, HW, C, G, silu, train):
     KC.case_groupnorm(DEV, B, HW, C, G, silu, train_params=train)
 
 
+@pytest.mark.parametrize("what,B,HW,C,G,knobs,lo,deferred", KC.GN_INSTANTIATION_CASES, ids=[c[0] for c in KC.GN_INSTANTIATION_CASES])
+def test_groupnorm_instantiations_no_other_case_reaches(what, B, HW, C, G, knobs, lo, deferred):
+    """two column chunks per thread, the remainder under "gn_unroll", the 512-thread 8-row forward, the 16-row forward and 512-thread
+    backward folding a deferred producer"""
+    KC.case_groupnorm_instantiation(DEV, B, HW, C, G, knobs, lo, deferred)
+
+
 @pytest.mark.parametrize("B,HW,Ca,Cb,G,silu", [(4, 4096, 320, 320, 32, True), (4, 4096, 640, 320, 32, True), (4, 1024, 640, 640, 32, True),
                                                (4, 1024, 1280, 640, 32, True), (4, 256, 1280, 1280, 32, True), (4, 64, 1280, 1280, 32, True),
                                                (1, 300, 64, 32, 8, False)])
