@@ -117,6 +117,22 @@ class ControlMixJob(C.Structure):
                 ("m", ControlMixMember * CONTROL_MIX_MAX_MEMBERS)]
 
 
+class ControlChainMember(C.Structure):
+    """mirror of clora_control_chain_member_t"""
+    _fields_ = [("Dh", C.c_void_p), ("ldd", C.c_int), ("U", C.c_void_p), ("ldu", C.c_int), ("Tc", C.c_void_p), ("ldt", C.c_int),
+                ("toff", C.c_int), ("r", C.c_int)]
+
+
+CONTROL_CHAIN_MAX_MEMBERS = 8  # CLORA_CONTROL_CHAIN_MAX_MEMBERS
+
+
+class ControlChainJob(C.Structure):
+    """mirror of clora_control_chain_job_t"""
+    _fields_ = [("H", C.c_void_p), ("ldh", C.c_int), ("Y", C.c_void_p), ("ldy", C.c_int), ("G", C.c_void_p), ("ldg", C.c_int),
+                ("M", C.c_int), ("C", C.c_int), ("rows_t", C.c_int), ("nmem", C.c_int), ("scale", C.c_float),
+                ("m", ControlChainMember * CONTROL_CHAIN_MAX_MEMBERS)]
+
+
 class LoraWgradJob(C.Structure):
     """mirror of clora_lora_wgrad_job_t"""
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int), ("T", C.c_void_p), ("ldt", C.c_int), ("toff", C.c_int), ("G", C.c_void_p),
@@ -187,6 +203,7 @@ _PROTOS = {
     "clora_lora_up_multi_f16": [C.POINTER(LoraUpJob), _I, _P],
     "clora_lora_fold_f16": [_P, _I, _P],
     "clora_control_mix_q_f16": [C.POINTER(ControlMixJob), _P],
+    "clora_control_chain_f16": [C.POINTER(ControlChainJob), _P],
     "clora_lora_wgrad_f16": [_P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _Z, _P],
     "clora_comm_unique_id": [_P],
     "clora_comm_init": [_P, _I, _I],

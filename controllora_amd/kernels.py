@@ -813,6 +813,41 @@ def control_mix_q(y, n_cols, members, rows_t):
     return y
 
 
+def control_chain_job(h, y, members, G, scale, rows_t):
+    """the host-side job of control_chain (include/clora.h clora_control_chain_job_t): h, y fp16 [M, C] (y may be h itself);
+    members = [(Dh fp32 [r, C] -- usually the first C columns of a [r, C + Cc] down matrix --, U fp32 [C, r], Tc fp32 [rows_t, >=
+    toff + r], toff), ...] in chain order; G fp32 [R, R] (None for one member).  What the library cannot see (dtypes, the buffers'
+    extents) is checked here; its own contract (sizes, ranks, member count, overlap) is the library's to refuse."""
+    if h.dim() != 2 or y.dim() != 2 or h.stride(1) != 1 or y.stride(1) != 1 or tuple(h.shape) != tuple(y.shape):
+        raise capi.CloraError(f"control_chain: input {tuple(h.shape)} / output {tuple(y.shape)} with strides {h.stride()} / {y.stride()}")
+    if len(members) > capi.CONTROL_CHAIN_MAX_MEMBERS:
+        raise capi.CloraError(f"a control chain job takes at most {capi.CONTROL_CHAIN_MAX_MEMBERS} members, got {len(members)}")
+    M, C_ = h.shape
+    R = sum(m[1].shape[1] for m in members)
+    if G is not None and (G.dim() != 2 or G.stride(1) != 1 or G.shape[0] < R or G.shape[1] < R):
+        raise capi.CloraError(f"control_chain: G {tuple(G.shape)} for {R} stacked ranks")
+    if G is None and len(members) > 1:
+        raise capi.CloraError("control_chain: several members need G")
+    job = capi.ControlChainJob(ptr(h, f16), h.stride(0), ptr(y, f16), y.stride(0), ptr(G, f32) if G is not None else None,
+                               G.stride(0) if G is not None else 0, M, C_, int(rows_t), len(members), float(scale))
+    for i, (Dh, U, Tc, toff) in enumerate(members):
+        r = U.shape[1]
+        if Dh.dim() != 2 or U.dim() != 2 or Tc.dim() != 2 or Dh.stride(1) != 1 or U.stride(1) != 1 or Tc.stride(1) != 1 or \
+                tuple(Dh.shape) != (r, C_) or U.shape[0] != C_ or Tc.shape[0] != rows_t or toff < 0 or toff + r > Tc.shape[1]:
+            raise capi.CloraError(f"control_chain: member {i} has Dh {tuple(Dh.shape)}, U {tuple(U.shape)} and Tc {tuple(Tc.shape)} "
+                                  f"(offset {toff}) for {rows_t} control rows and {C_} columns")
+        job.m[i] = capi.ControlChainMember(ptr(Dh, f32), Dh.stride(0), ptr(U, f32), U.stride(0), ptr(Tc, f32), Tc.stride(0), int(toff), r)
+    job._keep = (h, y, G, members)                 # the operands outlive the launches that are built from this job
+    return job
+
+
+def control_chain(h, y, members, G, scale, rows_t):
+    """y = fp16(h + scale * U t) with t the rank-space solution of a chain of frozen V2 control processors (include/clora.h
+    clora_control_chain_f16): one launch that reads h once and writes y once -> y"""
+    _call("clora_control_chain_f16", C.byref(control_chain_job(h, y, members, G, scale, rows_t)), nbytes=4.0 * h.shape[0] * h.shape[1])
+    return y
+
+
 def lora_down_multi(jobs):
     """several adapter down-projections (possibly over different inputs) in one launch"""
     for i in range(0, len(jobs), capi.LORA_MAX_JOBS):

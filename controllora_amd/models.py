@@ -14,8 +14,9 @@ score matrix; here a site is: (control add) -> one fused q|k|v GEMM with the ran
 -> flash attention -> one out-projection GEMM (+ adapter + bias + residual).  Quirks C1-C9 of SURVEY.md
 Appendix C are kept.  ``post_add=True`` and ``pre_loras`` / ``post_loras`` chains run the
 same kernels unfused in the reference's exact order (`_generic_call`); frozen chained members -- plain LoRAs, and with a second
-ControlLoRA (canny + pose, `mix_control_loras`) version-1 control processors -- can instead be folded into the frozen weights
-(`fold_sites`), the control members' guide-only share being one more launch on the q block (`_control_mix`).
+ControlLoRA (canny + pose, `mix_control_loras`) control processors of the main model's version -- can instead be folded into the
+frozen weights (`fold_sites`): a v1 member's guide-only share is one more launch on the q block (`_control_mix`), the control adds of
+a v2 chain are one launch per side of the site (`_control_chain`).
 """
 from __future__ import annotations
 
@@ -273,8 +274,24 @@ class LoRACrossAttnProcessor(nn.Module):
         control_ok = getattr(self, "fold_control_members", False)
         for m in members:
             control = control_ok and type(m) is ControlLoRACrossAttnProcessor
-            if type(m) is not LoRACrossAttnProcessor and not control:
+            control2 = control_ok and type(m) is ControlLoRACrossAttnProcessorV2
+            if type(m) is not LoRACrossAttnProcessor and not control and not control2:
                 return f"a member is a {type(m).__name__}, not a plain LoRACrossAttnProcessor"
+            if control2:
+                # a frozen v2 control member: its q / out adapters fold like a plain member's (they read the chain's final hidden
+                # states, as the base projections do), its control adds join the site's `_control_chain` launches
+                if getattr(self, "version", 0) != 2:
+                    return "a member is a version-2 control processor and the main processor is not version 2"
+                if m._chain_members():
+                    return "a control member has a chain of its own"
+                if max(m.to_control.down.weight.shape[0], m.to_control_out.down.weight.shape[0]) > 16:
+                    return "a control member's control adapter has a rank above 16"
+                if m.to_control.down.weight.shape[1] % 4 or m.to_control_out.down.weight.shape[1] % 4:
+                    return "a control member's hidden size plus control channels is not a multiple of 4"
+                if m.control_states is None:
+                    return "a control member has no control states injected"
+                if torch.is_grad_enabled():
+                    return "a member is a control processor and autograd is on"
             if control:
                 # a frozen v1 control member: its adapters fold like a plain member's, its control share is `_control_mix`
                 if getattr(self, "version", 0) != 1:
@@ -300,6 +317,19 @@ class LoRACrossAttnProcessor(nn.Module):
         ctl = [m for m in members if type(m) is ControlLoRACrossAttnProcessor]
         if len(ctl) > K.capi.CONTROL_MIX_MAX_MEMBERS or sum(m.to_q_lora.down.weight.shape[0] for m in ctl) > 32:
             return f"more than {K.capi.CONTROL_MIX_MAX_MEMBERS} control members, or their q adapters' ranks sum to more than 32"
+        if any(type(m) is ControlLoRACrossAttnProcessorV2 for m in members):
+            # the chain launch (clora_control_chain_f16) carries the main processor's own control adapters at their place in the order
+            v2 = [p for p in list(getattr(self, "pre_loras", [])) + [self] + list(getattr(self, "post_loras", []))
+                  if isinstance(p, ControlLoRACrossAttnProcessorV2)]
+            if self.hidden_size % 8 or self.hidden_size > 2560:
+                return "the hidden size is no multiple of 8 or above 2560"
+            if any(l.down.weight.shape[0] > 16 or l.down.weight.shape[1] % 4 or l.down.weight.dtype != f32 or l.up.weight.dtype != f32
+                   for l in (self.to_control, self.to_control_out)):
+                return "the main processor's control adapters are not fp32 of rank 16 or less over a multiple of 4 channels"
+            if len(v2) > K.capi.CONTROL_CHAIN_MAX_MEMBERS or max(sum(getattr(p, n).down.weight.shape[0] for p in v2)
+                                                                 for n in ("to_control", "to_control_out")) > 32:
+                return (f"more than {K.capi.CONTROL_CHAIN_MAX_MEMBERS} version-2 control processors at the site, or their control "
+                        "adapters' ranks sum to more than 32")
         return None
 
     def _control_mix(self, B, N, dtype, scale):
@@ -480,7 +510,8 @@ def fold_sites(pairs, scale=1.0):
     refolds.  Scaling quirks as in `_generic_call`: a member's value adapter is scaled by `scale` only under a version-0 main
     processor, else by 1.0 (C3); a member's key / value / out adapter is left out when that member's own skip flag is set.
     A frozen version-1 control member (`fold_control_members`) hands over its q / k / v / out adapters exactly as a plain member
-    does; what its control map adds to q is not a weight and is the site's `_control_mix`.
+    does; what its control map adds to q is not a weight and is the site's `_control_mix`.  A frozen version-2 control member of a
+    version-2 site hands over its q / out adapters (it has no k / v adapters); its control adds are the site's `_control_chain`.
     -> number of sites that were (re)folded."""
     scale = float(scale)
     jobs, fresh = [], []
@@ -526,7 +557,9 @@ def fold_sites(pairs, scale=1.0):
 
 class _ControlMixin:
     fold_chain = False        # opt-in: frozen plain LoRAs chained onto this site ride in its frozen weights (fold_sites)
-    fold_control_members = False   # opt-in beside it: frozen v1 control members fold too (LoRACrossAttnProcessor._control_mix)
+    # opt-in beside it: frozen control members fold too -- v1 members of a v1 site (LoRACrossAttnProcessor._control_mix), v2 members
+    # of a v2 site (ControlLoRACrossAttnProcessorV2._control_chain)
+    fold_control_members = False
 
     def inject_pre_lora(self, lora_layer):
         self.pre_loras.append(lora_layer)
@@ -648,6 +681,65 @@ class ControlLoRACrossAttnProcessorV2(_ControlMixin, LoRACrossAttnProcessor):
         self.pre_loras: List[LoRACrossAttnProcessor] = []
         self.post_loras: List[LoRACrossAttnProcessor] = []
 
+    def _control_chain(self, B, N, dtype, scale):
+        """-> dict(in=(members, G), out=(members, G), rows_t) for kernels.control_chain, or None when no version-2 control member
+        is chained on.  Only reached on the folded path (`_fold_blocker` is None).  Every V2 processor i of the chain (pre
+        members, this processor, post members) updates the hidden states in turn (reference models.py:366-372, 412-418):
+        t_i = Dh_i h_{i-1} + Dc_i ctrl_i, h_i = h_{i-1} + s U_i t_i.  The job holds, per side (to_control before to_q,
+        to_control_out before to_out), the members' Dh (a view of the down matrix), U, the guide's share Tc_i = Dc_i ctrl_i [rows_t,
+        r] -- the one the member model's forward left (`_control_parts`) or one `lora_down` on the control tokens -- and
+        G = Dh U of the stacked adapters at scale 1 (weights only: evaluated here, once per key, not per step).  Keyed like
+        `_control_mix`: control states and parameters by storage / version, the chain in order, scale, B, N."""
+        procs = [p for p in list(self.pre_loras) + [self] + list(self.post_loras) if isinstance(p, ControlLoRACrossAttnProcessorV2)]
+        if len(procs) < 2:
+            return None
+        scale = float(scale)
+        C_ = self.hidden_size
+        probe = torch.empty((B, N, 0), dtype=dtype)
+        ctrls, partss, key = [], [], [scale, B, N]
+        for p in procs:
+            ctrl = p._control_tokens(probe)                 # [b, N, Cc]; raises for a control batch that does not divide B
+            if ctrl.shape[1] != N:
+                raise ValueError(f"a control processor's map has {ctrl.shape[1]} tokens, the site has {N}")
+            layers = (p.to_control, p.to_control_out)
+            parts = getattr(p, "_control_parts", None)
+            if not (parts and ctrl.shape[0] * N == parts["rows"] and all(id(l) in parts for l in layers)):
+                parts = None
+            src = p.control_states                          # (as injected: `ctrl` may be a cast made for this call)
+            key.append((id(p), id(src), src.data_ptr(), src._version, tuple(src.shape),
+                        tuple((w.data_ptr(), w._version) for l in layers for w in (l.down.weight, l.up.weight)),
+                        None if parts is None else tuple(id(parts[id(l)]) for l in layers)))
+            ctrls.append(ctrl)
+            partss.append(parts)
+        key = tuple(key)
+        st = self.__dict__.get("_chain")
+        if st is not None and st["key"] == key:
+            return st
+        if K.capi.lib().require_device and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a chained adapter, its scale or the frozen weights changed inside a graph capture: run one forward "
+                               "(or ControlLoRA.fold_now) before capturing, the fold is not part of the captured step")
+        rows_t = max(c.shape[0] for c in ctrls) * N
+        st = dict(key=key, rows_t=rows_t, keep=(ctrls, partss, [p.control_states for p in procs]))
+        with torch.no_grad():
+            for side, name in (("in", "to_control"), ("out", "to_control_out")):
+                mem = []
+                for p, ctrl, parts in zip(procs, ctrls, partss):
+                    layer = getattr(p, name)
+                    D, Uw = layer.down.weight.detach(), layer.up.weight.detach()
+                    if parts is not None:
+                        Tc = parts[id(layer)].detach()
+                    else:
+                        c2 = _flat2(ctrl)
+                        Tc = K.lora_down(c2, D[:, C_:], torch.empty((c2.shape[0], D.shape[0]), dtype=f32, device=c2.device), 0,
+                                         c2.shape[0], D.shape[1] - C_)
+                    if Tc.shape[0] != rows_t:               # a control batch of 1 beside one of B: tile it once
+                        Tc = Tc.repeat(rows_t // Tc.shape[0], 1)
+                    mem.append((D[:, :C_], Uw, Tc, 0))
+                G = (torch.cat([m[0] for m in mem], 0).double() @ torch.cat([m[1] for m in mem], 1).double()).float().contiguous()
+                st[side] = (mem, G)
+        self.__dict__["_chain"] = st
+        return st
+
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, scale=1.0, residual=None):
         assert self.control_states is not None
         attn = _host(attn, encoder_hidden_states)
@@ -657,11 +749,21 @@ class ControlLoRACrossAttnProcessorV2(_ControlMixin, LoRACrossAttnProcessor):
         B, N, C_ = hidden_states.shape
         e2 = _flat2(encoder_hidden_states) if attn.is_cross else None
         Nk = encoder_hidden_states.shape[1] if attn.is_cross else N
-        hp = self.process_control_states(hidden_states, scale)       # h' replaces h everywhere (models.py:369)
         shape3 = hidden_states.shape
+        chain = self._control_chain(B, N, hidden_states.dtype, scale)
+        if chain is not None:
+            # frozen v2 control members folded on (`_fold_blocker` is None): the control adds of the whole chain, this processor's
+            # own at its place in the order, are ONE launch per side instead of one `process_control_states` per processor
+            h2 = _flat2(hidden_states)
+            hp = K.control_chain(h2, torch.empty_like(h2), *chain["in"], scale, chain["rows_t"])
 
-        def post(a):                                                  # a' = a + control_out term (models.py:415)
-            return self.process_control_states(a.reshape(shape3), scale, is_out=True)
+            def post(a):
+                return K.control_chain(a, a, *chain["out"], scale, chain["rows_t"])      # in place: `a` is this call's own
+        else:
+            hp = self.process_control_states(hidden_states, scale)   # h' replaces h everywhere (models.py:369)
+
+            def post(a):                                              # a' = a + control_out term (models.py:415)
+                return self.process_control_states(a.reshape(shape3), scale, is_out=True)
 
         out = self._attend(attn, hp, hp, e2, B, N, Nk, scale, post, residual, own_out_always=True)
         return out.reshape(B, N, C_)
@@ -867,7 +969,8 @@ class ControlLoRA(nn.Module):
 
     def fold_chains(self, enabled: bool = True, control_members: bool = False):
         """opt in (or out): every site whose chain is eligible (`fold_report`) runs the fused path on W + s U D;
-        control_members: frozen version-1 ControlLoRA processors chained on (models.mix_control_loras) are eligible too"""
+        control_members: frozen ControlLoRA processors of the main model's version chained on (models.mix_control_loras) are
+        eligible too"""
         for _, p in self._named_processors():
             p.fold_chain = bool(enabled)
             p.fold_control_members = bool(enabled and control_members)
@@ -875,6 +978,7 @@ class ControlLoRA(nn.Module):
                 p.__dict__.pop("_fold", None)
             if not p.fold_control_members:
                 p.__dict__.pop("_mix", None)
+                p.__dict__.pop("_chain", None)
         return self
 
     def fold_report(self) -> dict:

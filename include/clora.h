@@ -582,6 +582,41 @@ typedef struct {
     clora_control_mix_member_t m[CLORA_CONTROL_MIX_MAX_MEMBERS];
 } clora_control_mix_job_t;
 int clora_control_mix_q_f16(const clora_control_mix_job_t* job, void* stream);
+/* The control adds of a chain of frozen VERSION-2 ControlLoRA processors at one side of an attention site (before to_q, or before
+ * to_out on the attention output) in one launch.  In the reference every V2 processor i of the chain updates the hidden states in
+ * turn (models.py:366-372, 412-418): t_i = Dh_i h_{i-1} + Dc_i ctrl_i, h_i = h_{i-1} + s U_i t_i, with to_control.down split into
+ * its hidden (Dh) and control (Dc) columns.  Dh_i h_{i-1} = Dh_i h + s sum_{j<i} (Dh_i U_j) t_j, so with a, b indexing the stacked
+ * ranks (R = sum r_i) and member(.) the member a stacked rank belongs to:
+ *   p[m,a] = sum_k Dh[a,k] * float(H[m,k]) + Tc[m % rows_t, a]
+ *   t[m,a] = p[m,a] + scale * sum_{b : member(b) < member(a)} G[a,b] * t[m,b]
+ *   Y[m,n] = fp16( float(H[m,n]) + scale * sum_a U[n,a] * t[m,a] )
+ * H, Y: fp16 [M, C] with row pitches ldh, ldy, 16-byte aligned.  Y is a buffer disjoint from H, or H itself with the same pitch
+ * (every row is read completely before it is written); any other overlap is refused.  Member i: Dh_i fp32 [r_i, C] with row pitch
+ * ldd (the first C columns of the layer's [r, C + Cc] down matrix: ldd = C + Cc), 16-byte aligned, ldd % 4 == 0; U_i fp32 [C, r_i]
+ * with row pitch ldu; Tc_i fp32 [rows_t, ..] with row pitch ldt at column offset toff: Dc_i ctrl_i, which depends on the guide alone.
+ * G: fp32 [R, R] with row pitch ldg, of which only the blocks below the block diagonal are read: block (i, j), j < i, is Dh_i U_j
+ * (no scale); may be NULL for a single member.  rows_t: the tokens of one image for a control batch of 1, or M.
+ * C % 8 == 0, C <= 2560 (the row tile is register resident), ldh % 8 == ldy % 8 == 0, ldh, ldy >= C, 1 <= r_i <= 16, R <= 32,
+ * 1 <= nmem <= CLORA_CONTROL_CHAIN_MAX_MEMBERS, M % rows_t == 0: a job that breaks this returns CLORA_ERR_ARG and launches nothing.
+ * `job` is HOST memory, read at the call.  All sums are fp32 in a fixed order (a lane's columns ascending, the lanes of a row in a
+ * fixed butterfly, members in order, ranks in order), the operands stay fp32, nothing is rounded before the store.  Deterministic:
+ * no atomics, every element is produced by one thread. */
+#define CLORA_CONTROL_CHAIN_MAX_MEMBERS 8
+typedef struct {
+    const float* Dh; int ldd;
+    const float* U; int ldu;
+    const float* Tc; int ldt, toff;
+    int r;
+} clora_control_chain_member_t;
+typedef struct {
+    const clora_half* H; int ldh;
+    clora_half* Y; int ldy;
+    const float* G; int ldg;
+    int M, C, rows_t, nmem;
+    float scale;
+    clora_control_chain_member_t m[CLORA_CONTROL_CHAIN_MAX_MEMBERS];
+} clora_control_chain_job_t;
+int clora_control_chain_f16(const clora_control_chain_job_t* job, void* stream);
 /* G[n*gs_n + j*gs_j] += scale * sum_m A[m, n] * T[m, toff+j]  (adapter weight gradients; two-stage
  * deterministic reduction through `workspace` of clora_lora_wgrad_workspace_bytes(M, N, R) bytes, no atomics). */
 size_t clora_lora_wgrad_workspace_bytes(int M, int N, int R);
