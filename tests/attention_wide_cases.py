@@ -73,6 +73,17 @@ def case_fused_168(dev):
     assert bool(torch.isnan(obuf[spare].float()).all()), "the forward wrote outside its column block"
 
 
+STRIDES = (2, 1, 70, 100, 256)
+
+
+def case_strides(dev, dims=STRIDES):
+    """kernel_cases.case_attention_strides for the wide kernel, forward only: q, k, v and o are column blocks (from column 8) of four
+    NaN-filled buffers under four different row strides, two batch elements; a K or V tile fetched with the other operand's stride
+    brings NaN into o, a store with a wrong stride lands outside o's block"""
+    assert dims[4] > K.attn_max_head_dim(True)
+    KC.attention_strides_check(KC.attention_strides_inputs(dev, *dims, backward=False), tag=" wide")
+
+
 def case_one_key(dev):
     """one key: every weight is exactly 1, so every output row is v[0] bit for bit"""
     dims = B, H, Nq, Nk, D = SHAPES["one_key"]

@@ -777,8 +777,8 @@ def case_attention_negative_logits(dev, B, H, Nq, Nk, D, seed=31):
     dO = rnd((B * Nq, H * D), dev, g)
     dq, dk, dv = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2)
     K.attn_bwd(q2, k2, v2, o, dO, lse, B, H, Nq, Nk, D, scale, dq, dk, dv)
-    for t_ in (dq, dk, dv):
-        assert bool(torch.isfinite(t_.float()).all())
+    for name, t_ in (("dq", dq), ("dk", dk), ("dv", dv)):
+        assert bool(torch.isfinite(t_.float()).all()), (name, "a NaN / inf was computed")
 
 
 def case_attention_block_order(dev, B, H, Nq, Nk, D, seed=23):
@@ -1566,8 +1566,10 @@ def attention_full_inputs(dev, B, H, Nq, Nk, D, q_scale=1.0, seed=51):
     return dict(q=q, k=k, v=v, dO=dO, scale=scale, dims=(B, H, Nq, Nk, D), q_scale=q_scale, ref=_attn_ref64(q, k, v, dO, B, H, Nq, Nk, D, scale))
 
 
-def attention_full_check(inp, strided=False, tag=""):
-    """one forward + backward of the library on prepared inputs, every output against the fp64 reference (case_attention_full)"""
+def attention_full_check(inp, strided=False, tag="", bwd=None):
+    """one forward + backward of the library on prepared inputs, every output against the fp64 reference (case_attention_full);
+    `bwd`: called in place of K.attn_bwd with its arguments (case_attention_workspace hands the C entry point a workspace of its own)"""
+    bwd = bwd or K.attn_bwd
     B, H, Nq, Nk, D = inp["dims"]
     q, k, v, dO, scale, ref = inp["q"], inp["k"], inp["v"], inp["dO"], inp["scale"], inp["ref"]
     dev, HD = q.device, H * D
@@ -1578,7 +1580,7 @@ def attention_full_check(inp, strided=False, tag=""):
         dq, dk, dv = buf[:B * Nq, :HD], buf[:B * Nk, HD:2 * HD], buf[:B * Nk, 2 * HD:3 * HD]
     else:
         dq, dk, dv = (torch.full((n, HD), nan, dtype=f16, device=dev) for n in (B * Nq, B * Nk, B * Nk))
-    K.attn_bwd(q, k, v, o, dO, lse, B, H, Nq, Nk, D, scale, dq, dk, dv)
+    bwd(q, k, v, o, dO, lse, B, H, Nq, Nk, D, scale, dq, dk, dv)
     errs = {"o": rel64(o, ref["o"])}
     # LSE, per row: the kernel rounds q * scale * log2(e) to fp16 once (<= 2^-12 relative per term of the logit); the factor 2 covers
     # the fp32 accumulation and log2f
@@ -1629,6 +1631,156 @@ def case_attention_widths(dev, B, H, Nq, Nk, D, widths=ATTN_WIDTHS, strided=Fals
             base = outs
         for name, a, b_ in zip(("o", "lse", "dq", "dk", "dv"), base, outs):
             assert torch.equal(a, b_), f"{name}: bwd {bw} / fwd {fw} waves differ from {widths[0]} in {int((a != b_).sum())} elements"
+
+
+ATTN_OPERANDS = ("q", "k", "v", "o", "dO", "dq", "dk", "dv")      # the eight row-strided operands of the attention entry points
+
+
+def attn_strides(HD):
+    """eight pairwise different row strides, all multiples of 8 and at least HD + 16: every operand's column block starts at column 8
+    of its own buffer and has spare columns on both sides"""
+    return {name: HD + 8 * (i + 2) for i, name in enumerate(ATTN_OPERANDS)}
+
+
+def _attn_arena(rows, HD, ld, max_ld, dev, gen=None):
+    """a NaN-filled buffer of (rows + 2) * max_ld halves and the [rows, HD] column block at column 8 with row stride ld in it (random
+    values with `gen`): an access with ANY of the eight strides stays inside the allocation, a read with another operand's stride picks
+    up NaN, a store with another operand's stride lands on a NaN outside the block"""
+    buf = torch.full(((rows + 2) * max_ld,), float("nan"), dtype=f16, device=dev)
+    view = buf.as_strided((rows, HD), (ld, 1), 8)
+    if gen is not None:
+        view.copy_(rnd((rows, HD), dev, gen))
+    return buf, view
+
+
+def attention_strides_inputs(dev, B, H, Nq, Nk, D, causal=False, backward=True, seed=101):
+    HD, scale = H * D, D ** -0.5
+    ld = attn_strides(HD)
+    g = torch.Generator().manual_seed(seed)
+    rows = {name: B * (Nq if name in ("q", "o", "dO", "dq") else Nk) for name in ATTN_OPERANDS}
+    inp = dict(dims=(B, H, Nq, Nk, D), scale=scale, ld=ld, rows=rows, causal=causal, backward=backward)
+    for name in ("q", "k", "v") + (("dO",) if backward else ()):
+        inp[name] = _attn_arena(rows[name], HD, ld[name], max(ld.values()), dev, g)[1]
+    inp["ref"] = _attn_ref64(inp["q"], inp["k"], inp["v"], inp.get("dO"), B, H, Nq, Nk, D, scale, causal=causal)
+    return inp
+
+
+def attention_strides_check(inp, tag=""):
+    """one forward (+ backward) on the inputs of attention_strides_inputs with fresh NaN-filled output buffers; every assertion names
+    the output that is wrong"""
+    B, H, Nq, Nk, D = inp["dims"]
+    q, k, v, scale, ref, ld, rows = inp["q"], inp["k"], inp["v"], inp["scale"], inp["ref"], inp["ld"], inp["rows"]
+    dev, HD, max_ld = q.device, H * D, max(inp["ld"].values())
+    new = lambda name: _attn_arena(rows[name], HD, ld[name], max_ld, dev)
+
+    def check(name, got, buf, lim):
+        finite = bool(torch.isfinite(got.float()).all())
+        e = rel64(got, ref[name]) if finite else float("nan")
+        print(f"ATTN_STRIDES{tag} {inp['dims']} causal={inp['causal']} {name}={e:.2e}")
+        assert finite, (name, "not every element is finite: unwritten, or computed from an operand read with another operand's row stride")
+        assert e < lim, (name, e)
+        try:
+            no_outliers(got, ref[name], name)
+        except AssertionError as err:
+            raise AssertionError((name, str(err))) from None
+        rest = buf.clone()
+        rest.as_strided((rows[name], HD), (ld[name], 1), 8).fill_(float("nan"))
+        assert bool(torch.isnan(rest.float()).all()), (name, "the kernel wrote outside the operand's column block")
+
+    obuf, o = new("o")
+    if inp["causal"]:
+        assert Nq == Nk
+        K.attn_fwd_causal(q, k, v, B, H, Nq, D, scale, out=o)
+        lse = None
+    else:
+        _, lse = K.attn_fwd(q, k, v, B, H, Nq, Nk, D, scale, out=o)
+    check("o", o, obuf, 2e-3)
+    if lse is not None:
+        bound = 2.0 ** -11 * ref["mag"] + 1e-5               # attention_full_check: the one fp16 rounding of the scaled query
+        lse_err = (lse.double() - ref["lse"]).abs()
+        assert bool(torch.isfinite(lse).all()) and bool((lse_err <= bound).all()), ("lse", float(lse_err.max()), float(bound.max()))
+    if not inp["backward"]:
+        return
+    (qbuf, dq), (kbuf, dk), (vbuf, dv) = new("dq"), new("dk"), new("dv")
+    K.attn_bwd(q, k, v, o, inp["dO"], lse, B, H, Nq, Nk, D, scale, dq, dk, dv)
+    for name, got, buf in (("dq", dq, qbuf), ("dk", dk, kbuf), ("dv", dv, vbuf)):
+        check(name, got, buf, 4e-3)
+
+
+def case_attention_strides(dev, B, H, Nq, Nk, D, causal=False, waves=(0,)):
+    """The eight leading dimensions of the attention entry points are independent: q, k, v, o, dO, dq, dk, dv are each a column block
+    (from column 8) of a NaN-filled buffer of its own, under eight pairwise different row strides.  Against fp64 on the same inputs: o
+    within 2e-3, dq / dk / dv within 4e-3 norm-wise and without outliers, the LSE under the bound of case_attention_full, every output
+    element finite, and everything outside an output's block still NaN.  A kernel that addresses one operand with another's stride reads
+    NaN or stores outside its block; the buffers are sized so that even then no access leaves them.  causal: clora_attn_fwd_causal_f16
+    with its four strides, forward only.  waves: the "attn_bwd_waves" / "attn_fwd_waves" values to run under (0 = the library's choice)."""
+    inp = attention_strides_inputs(dev, B, H, Nq, Nk, D, causal=causal, backward=not causal)
+    for w in waves:
+        if not w:
+            attention_strides_check(inp)
+            continue
+        with options(attn_bwd_waves=w, attn_fwd_waves=w):
+            attention_strides_check(inp, tag=f"[{w} waves]")
+
+
+def attn_bwd_workspace_bytes(dev, B, H, Nk, D):
+    """what K.attn_bwd hands clora_attn_bwd_f16 as its split workspace"""
+    return K.workspace(16 * 2 * B * Nk * H * D * 4, dev).numel() if Nk <= 1024 else 0
+
+
+def attn_split_count(B, H, Nq, Nk, D, workspace_bytes):
+    """The number of query splits of clora_attn_bwd_f16's dK/dV launch, restated from its host code: fewer than 256 blocks of 128 keys
+    and at least 512 queries split into ns = min(512 / key blocks, Nq / 128, workspace / one fp32 dK | dV slab pair) parts of
+    q_per_split = cdiv(Nq, ns) rounded up to 64 rows.  1: the unsplit kernel."""
+    cdiv = lambda a, b_: -(-a // b_)
+    kv_blocks = cdiv(Nk, 128) * B * H
+    if kv_blocks >= 256 or Nq < 512 or workspace_bytes <= 0 or D % 4:
+        return 1
+    ns = min(512 // kv_blocks, Nq // 128, workspace_bytes // (2 * B * Nk * H * D * 4))
+    return cdiv(Nq, cdiv(cdiv(Nq, ns), 64) * 64) if ns > 1 else 1
+
+
+def case_attention_split(dev, B, H, Nq, Nk, D, splits, strided=True, tail=False):
+    """case_attention_full on a shape that takes the query-split dK/dV path (per-split fp32 slabs, folded by attn_dkv_convert_kernel).
+    The split count the shape is chosen for is asserted from the restated rule, so a change of the rule fails here instead of silently
+    leaving the path.  tail: the fold's unrolled group of four slab pairs is followed by a tail of two or three."""
+    got = attn_split_count(B, H, Nq, Nk, D, attn_bwd_workspace_bytes(dev, B, H, Nk, D))
+    assert got == splits, f"{(B, H, Nq, Nk, D)} is split {got} ways, the case was written for {splits}"
+    assert not tail or (got >= 6 and got % 4 >= 2), f"{got} splits: no fold tail of two or more slab pairs after a full group"
+    return case_attention_full(dev, B, H, Nq, Nk, D, strided=strided)
+
+
+WS_SENTINEL = 0xA5
+
+
+def case_attention_workspace(dev, B, H, Nq, Nk, D, pairs=2.5):
+    """clora_attn_bwd_f16 called directly with a workspace_bytes of `pairs` slab pairs on a shape that would take more splits: the same
+    fp64 checks as case_attention_full, and every byte past the stated budget keeps its sentinel (the region is the head of a larger
+    buffer that holds the Nq / 128 slab pairs no split count can exceed, so an ignored budget is seen, not a stray store).  Then the
+    same shape with a NULL workspace: the unsplit kernel on a shape that would otherwise split."""
+    from controllora_amd import capi
+    slab = 2 * B * Nk * H * D * 4
+    budget = int(pairs * slab)
+    free, held = attn_split_count(B, H, Nq, Nk, D, 1 << 62), attn_split_count(B, H, Nq, Nk, D, budget)
+    assert 1 < held < free, f"{(B, H, Nq, Nk, D)}: {free} splits without a budget, {held} under {pairs} slab pairs"
+    inp = attention_full_inputs(dev, B, H, Nq, Nk, D)
+    arena = torch.full(((Nq // 128) * slab + 64,), WS_SENTINEL, dtype=torch.uint8, device=dev)
+
+    def bwd_with(ws, nbytes):
+        def bwd(q, k, v, o, dO, lse, B, H, Nq, Nk, D, scale, dq, dk, dv):
+            delta = torch.empty((B, H, Nq), dtype=f32, device=q.device)
+            capi.lib().call("clora_attn_bwd_f16", capi.ptr(q, f16), q.stride(0), capi.ptr(k, f16), k.stride(0), capi.ptr(v, f16), v.stride(0),
+                            capi.ptr(o, f16), o.stride(0), capi.ptr(dO, f16), dO.stride(0), capi.ptr(lse, f32), capi.ptr(delta),
+                            capi.ptr(dq, f16), dq.stride(0), capi.ptr(dk, f16), dk.stride(0), capi.ptr(dv, f16), dv.stride(0),
+                            B, H, Nq, Nk, D, float(scale), capi.ptr(ws), nbytes, capi.stream())
+        return bwd
+
+    attention_full_check(inp, strided=True, tag=f"[{pairs} slab pairs]", bwd=bwd_with(arena, budget))
+    past = int((arena[budget:] != WS_SENTINEL).sum())
+    assert past == 0, ("workspace", f"{past} bytes past the stated {budget} were written")
+    assert bool((arena[:held * slab] != WS_SENTINEL).any()), ("workspace", "the split path did not run")
+    attention_full_check(inp, strided=True, tag="[no workspace]", bwd=bwd_with(None, 0))
+    assert bool((arena[budget:] == WS_SENTINEL).all()), ("workspace", "written by a call that was given none")
 
 
 def case_attention_causal(dev, B, H, N, D, strided=True):

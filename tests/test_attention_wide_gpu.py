@@ -18,6 +18,10 @@ def test_wide_forward_fused_168():
     W.case_fused_168(DEV)
 
 
+def test_wide_forward_distinct_strides():
+    W.case_strides(DEV)
+
+
 def test_wide_forward_one_key():
     W.case_one_key(DEV)
 

@@ -544,6 +544,49 @@ def test_attention_causal_rejects_wide_heads():
     KC.case_attention_causal_rejects("cpu", 72)
 
 
+# ---- eight distinct leading dimensions; the query-split dK/dV path (tests/test_attention_mutants_emu.py: what each shape is for)
+ATTN_STRIDE_SHAPES = [(2, 2, 70, 150, 40), (2, 2, 70, 150, 64), (2, 1, 70, 150, 80), (2, 1, 40, 70, 160)]
+ATTN_STRIDE_SPLIT_SHAPES = [(2, 2, 513, 77, 40), (1, 2, 513, 77, 128)]
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D", ATTN_STRIDE_SHAPES + ATTN_STRIDE_SPLIT_SHAPES)
+def test_attention_distinct_strides(B, H, Nq, Nk, D):
+    """q, k, v, o, dO, dq, dk, dv under eight different row strides, two batch elements; the last two shapes take the split dK/dV path
+    and its fold kernel; head dims <= 64 also under the 8-wave kernels"""
+    KC.case_attention_strides("cpu", B, H, Nq, Nk, D, waves=(0, 8) if D <= 64 and Nq < 512 else (0,))
+
+
+def test_attention_causal_distinct_strides():
+    KC.case_attention_strides("cpu", 2, 2, 77, 77, 64, causal=True)
+
+
+@pytest.mark.parametrize("D", [8, 32, 40, 64, 80, 96, 128, 160])
+def test_attention_split_every_instantiation(D):
+    """every <DP, DT, BT> of the backward on the query-split path: three splits of 192 queries, the last with 129 rows (a ragged Q tile
+    at both tile heights), gradients as column blocks of one buffer"""
+    KC.case_attention_split("cpu", 2, 2, 513, 77, D, splits=3)
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D,splits", [(1, 1, 1100, 77, 40, 6), (1, 1, 1300, 77, 16, 7)])
+def test_attention_split_fold_tail(B, H, Nq, Nk, D, splits):
+    """the slab fold's unrolled group of four followed by a tail of two and of three slab pairs"""
+    KC.case_attention_split("cpu", B, H, Nq, Nk, D, splits=splits, strided=False, tail=True)
+
+
+def test_attention_split_five_ways():
+    """one unrolled group of the fold plus one tail slab pair"""
+    KC.case_attention_split("cpu", 1, 2, 640, 77, 40, splits=5)
+
+
+def test_attention_split_fold_second_grid_stride_trip():
+    """B * Nk * H * D = 2,293,760 > 2048 blocks x 256 threads x 4 elements: attn_dkv_convert_kernel's capped grid makes a second trip"""
+    KC.case_attention_split("cpu", 1, 14, 512, 1024, 160, splits=4)
+
+
+def test_attention_workspace_budget():
+    KC.case_attention_workspace("cpu", 2, 2, 1100, 77, 40)
+
+
 OPTION_VALUES = [("epi_hoist", 0), ("epi_two_phase", 0), ("gn_unroll", 1), ("gn_blocks", 64), ("gn_blocks", 4096),
                  ("strip_blocks", 64), ("strip_blocks", 16384), ("wgrad_patch", 128)]
 

@@ -593,6 +593,40 @@ def test_attention_causal_rejects_wide_heads():
     KC.case_attention_causal_rejects(DEV, 72)
 
 
+# ---- eight distinct leading dimensions; the query-split dK/dV path: the shapes of tests/test_kernels_emu.py (tests/test_attention_mutants_emu.py
+# says what each is for), a few milliseconds each on the device
+@pytest.mark.parametrize("B,H,Nq,Nk,D", [(2, 2, 70, 150, 40), (2, 2, 70, 150, 64), (2, 1, 70, 150, 80), (2, 1, 40, 70, 160),
+                                         (2, 2, 513, 77, 40), (1, 2, 513, 77, 128)])
+def test_attention_distinct_strides(B, H, Nq, Nk, D):
+    KC.case_attention_strides(DEV, B, H, Nq, Nk, D, waves=(0, 8) if D <= 64 and Nq < 512 else (0,))
+
+
+def test_attention_causal_distinct_strides():
+    KC.case_attention_strides(DEV, 2, 2, 77, 77, 64, causal=True)
+
+
+@pytest.mark.parametrize("D", [8, 32, 40, 64, 80, 96, 128, 160])
+def test_attention_split_every_instantiation(D):
+    KC.case_attention_split(DEV, 2, 2, 513, 77, D, splits=3)
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D,splits", [(1, 1, 1100, 77, 40, 6), (1, 1, 1300, 77, 16, 7)])
+def test_attention_split_fold_tail(B, H, Nq, Nk, D, splits):
+    KC.case_attention_split(DEV, B, H, Nq, Nk, D, splits=splits, strided=False, tail=True)
+
+
+def test_attention_split_five_ways():
+    KC.case_attention_split(DEV, 1, 2, 640, 77, 40, splits=5)
+
+
+def test_attention_split_fold_second_grid_stride_trip():
+    KC.case_attention_split(DEV, 1, 14, 512, 1024, 160, splits=4)
+
+
+def test_attention_workspace_budget():
+    KC.case_attention_workspace(DEV, 2, 2, 1100, 77, 40)
+
+
 OPTION_VALUES = [("epi_hoist", 0), ("epi_two_phase", 0), ("gn_unroll", 1), ("gn_blocks", 64), ("gn_blocks", 4096),
                  ("strip_blocks", 64), ("strip_blocks", 16384), ("wgrad_patch", 128)]
 
