@@ -57,8 +57,9 @@ def detect(img: np.ndarray, low, high, detector: str = "numpy", device="cuda") -
 
 
 def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, sample_steps, scale, seed, eta,
-            low_threshold, high_threshold, sampler="dpm", detector="numpy"):
-    """reference argument order; `eta` is accepted for compatibility (both samplers here are deterministic, eta = 0);
+            low_threshold, high_threshold, sampler="dpm", detector="numpy", sampler_step="host"):
+    """reference argument order; `eta` is DDIM's (0: deterministic; DPM-Solver++ has no such parameter and ignores it);
+    `sampler_step="device"` runs each scheduler step as one launch (controllora_amd.kernels.sampler_step);
     `detector="device"` makes the edge map with the HIP detector (controllora_amd.kernels.canny) instead of the numpy one"""
     import torch
     img = resize_image(hwc3(input_image), image_resolution)
@@ -67,7 +68,7 @@ def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_re
     if seed == -1:
         seed = random.randint(0, 65535)
     images = pipe(prompt, control, a_prompt=a_prompt, n_prompt=n_prompt, num_samples=num_samples, ddim_steps=sample_steps,
-                  scale=scale, seed=seed, sampler=sampler)
+                  scale=scale, seed=seed, sampler=sampler, eta=eta, step_impl=sampler_step)
     return [255 - detected_map] + [im.numpy() for im in images]
 
 
@@ -89,6 +90,8 @@ def main(argv=None):
     ap.add_argument("--low_threshold", type=int, default=100)
     ap.add_argument("--high_threshold", type=int, default=200)
     ap.add_argument("--sampler", default="dpm", choices=["dpm", "ddim"])
+    ap.add_argument("--sampler_step", default="host", choices=["host", "device"],
+                    help="scheduler step as torch ops on the latents (host) or as one HIP launch per step (device)")
     ap.add_argument("--detector", default="numpy", choices=["numpy", "device"], help="Canny on the CPU (numpy) or on the GPU (HIP kernels)")
     ap.add_argument("--out", default="canny2image.png")
     a = ap.parse_args(argv)
@@ -96,7 +99,8 @@ def main(argv=None):
     from controllora_amd.pipeline import ControlLoRAPipeline
     pipe = ControlLoRAPipeline.from_pretrained(a.base, a.control_lora)
     results = process(pipe, np.asarray(Image.open(a.input).convert("RGB")), a.prompt, a.a_prompt, a.n_prompt, a.num_samples,
-                      a.image_resolution, a.sample_steps, a.scale, a.seed, a.eta, a.low_threshold, a.high_threshold, a.sampler, a.detector)
+                      a.image_resolution, a.sample_steps, a.scale, a.seed, a.eta, a.low_threshold, a.high_threshold, a.sampler, a.detector,
+                      a.sampler_step)
     Image.fromarray(np.concatenate(results, axis=1)).save(a.out)
     print("wrote", a.out)
 

@@ -50,11 +50,11 @@ def load_guides(specs, input_image, image_resolution, low, high, detector):
     return shown, controls
 
 
-def process(pipe, guides_shown, controls, prompt, a_prompt, n_prompt, num_samples, sample_steps, scale, seed, sampler="dpm"):
+def process(pipe, guides_shown, controls, prompt, a_prompt, n_prompt, num_samples, sample_steps, scale, seed, sampler="dpm", sampler_step="host"):
     if seed == -1:
         seed = random.randint(0, 65535)
     images = pipe(prompt, controls, a_prompt=a_prompt, n_prompt=n_prompt, num_samples=num_samples, ddim_steps=sample_steps,
-                  scale=scale, seed=seed, sampler=sampler)
+                  scale=scale, seed=seed, sampler=sampler, step_impl=sampler_step)
     return list(guides_shown) + [im.numpy() for im in images]
 
 
@@ -76,6 +76,8 @@ def main(argv=None):
     ap.add_argument("--low_threshold", type=int, default=100)
     ap.add_argument("--high_threshold", type=int, default=200)
     ap.add_argument("--sampler", default="dpm", choices=["dpm", "ddim"])
+    ap.add_argument("--sampler_step", default="host", choices=["host", "device"],
+                    help="scheduler step as torch ops on the latents (host) or as one HIP launch per step (device)")
     ap.add_argument("--detector", default="numpy", choices=["numpy", "device"], help="Canny on the CPU (numpy) or on the GPU (HIP kernels)")
     ap.add_argument("--no_fold", action="store_true", help="keep the chained control models on the unfused path")
     ap.add_argument("--out", default="multi_control2image.png")
@@ -88,7 +90,8 @@ def main(argv=None):
     pipe = ControlLoRAPipeline.from_pretrained(a.base, list(a.control_lora), fold=not a.no_fold)
     inp = np.asarray(Image.open(a.input).convert("RGB")) if a.input else None
     shown, controls = load_guides(a.guide, inp, a.image_resolution, a.low_threshold, a.high_threshold, a.detector)
-    results = process(pipe, shown, controls, a.prompt, a.a_prompt, a.n_prompt, a.num_samples, a.sample_steps, a.scale, a.seed, a.sampler)
+    results = process(pipe, shown, controls, a.prompt, a.a_prompt, a.n_prompt, a.num_samples, a.sample_steps, a.scale, a.seed, a.sampler,
+                      a.sampler_step)
     with torch.no_grad():
         rep = pipe.control_lora[0].fold_report()
     fused = sum(r["folded"] for r in rep.values())

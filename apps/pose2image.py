@@ -37,10 +37,11 @@ def nearest_resize(img: np.ndarray, W: int, H: int) -> np.ndarray:
 
 
 def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, sample_steps, scale,
-            seed, eta, pose_map=None, sampler="dpm"):
+            seed, eta, pose_map=None, sampler="dpm", sampler_step="host"):
     """reference argument order (apps/gradio_pose2image.py:68) + `pose_map`: the annotator's output, supplied instead of computed
     (None: `input_image` IS the pose map).  `detect_resolution` only sized the annotator's input in the reference and is accepted
-    for compatibility; `eta` likewise (both samplers here are deterministic)."""
+    for compatibility.  `eta` is DDIM's (0: deterministic; DPM-Solver++ has no such parameter and ignores it); `sampler_step="device"`
+    runs each scheduler step as one launch (controllora_amd.kernels.sampler_step)."""
     import torch
     input_image = hwc3(input_image)
     detected_map = hwc3(pose_map if pose_map is not None else resize_image(input_image, detect_resolution))
@@ -51,7 +52,7 @@ def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_re
     if seed == -1:
         seed = random.randint(0, 65535)
     images = pipe(prompt, control, a_prompt=a_prompt, n_prompt=n_prompt, num_samples=num_samples, ddim_steps=sample_steps,
-                  scale=scale, seed=seed, sampler=sampler)
+                  scale=scale, seed=seed, sampler=sampler, eta=eta, step_impl=sampler_step)
     return [detected_map] + [im.numpy() for im in images]
 
 
@@ -73,6 +74,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=-1)
     ap.add_argument("--eta", type=float, default=0.0)
     ap.add_argument("--sampler", default="dpm", choices=["dpm", "ddim"])
+    ap.add_argument("--sampler_step", default="host", choices=["host", "device"],
+                    help="scheduler step as torch ops on the latents (host) or as one HIP launch per step (device)")
     ap.add_argument("--out", default="pose2image.png")
     a = ap.parse_args(argv)
     from PIL import Image
@@ -81,7 +84,7 @@ def main(argv=None):
     pose = np.asarray(Image.open(a.pose).convert("RGB"))
     photo = np.asarray(Image.open(a.input).convert("RGB")) if a.input else pose
     results = process(pipe, photo, a.prompt, a.a_prompt, a.n_prompt, a.num_samples, a.image_resolution, a.detect_resolution,
-                      a.sample_steps, a.scale, a.seed, a.eta, pose_map=pose, sampler=a.sampler)
+                      a.sample_steps, a.scale, a.seed, a.eta, pose_map=pose, sampler=a.sampler, sampler_step=a.sampler_step)
     Image.fromarray(np.concatenate(results, axis=1)).save(a.out)
     print("wrote", a.out)
 

@@ -152,12 +152,17 @@ class ConvUnpackJob(C.Structure):
                 ("Ci", C.c_int), ("ksize", C.c_int), ("Cip", C.c_int)]
 
 
+class SamplerCoef(C.Structure):
+    """mirror of clora_sampler_coef_t"""
+    _fields_ = [(n, C.c_float) for n in ("guidance", "x0_x", "x0_e", "k_x", "k_x0", "k_h", "k_e", "k_n")]
+
+
 LORA_MAX_JOBS = 16
 LORA_WGRAD_MAX_JOBS = 32       # CLORA_LORA_WGRAD_MAX_JOBS
 WGRAD_JOBS_PER_LAUNCH = min(LORA_WGRAD_MAX_JOBS, max(1, int(os.environ.get("CLORA_WGRAD_JOBS", "32"))))   # A/B runs: 16 = the round-5 batching
 CONV_MAX_JOBS = 32
 CANNY_MAX_GROUP = 64           # CLORA_CANNY_MAX_GROUP
-_P, _I, _Z, _F = C.c_void_p, C.c_int, C.c_size_t, C.c_float
+_P, _I, _Z, _F, _LL = C.c_void_p, C.c_int, C.c_size_t, C.c_float, C.c_longlong
 _PROTOS = {
     "clora_gemm_f16": [_P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _P, _Z, _P],
     "clora_gemm_f16_ex": [_P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(ConvDesc), C.POINTER(Epilogue), _I, _I, _P, _Z, _P],
@@ -230,6 +235,7 @@ _PROTOS = {
     "clora_canny_classify_u8": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "clora_canny_hysteresis_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "clora_canny_emit": [_P, _P, _P, _I, _I, _I, _P],
+    "clora_sampler_step_f16": [_P, _LL, _LL, _LL, _LL, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, C.POINTER(SamplerCoef), _P],
     "clora_abi_version": [],
     "clora_clock_probe": [_P, _I, _I, _P],
     "clora_groupnorm_workspace_bytes": [_I, _I, _I, _I, _I, _I],

@@ -1081,6 +1081,37 @@ def mse_weighted(pred, target, weights, sample_sums, dpred, grad_scale, loss_sca
           ptr(loss_scale, f32) if loss_scale is not None else None)
 
 
+SAMPLER_COEF_NAMES = tuple(n for n, _ in capi.SamplerCoef._fields_)
+
+
+def sampler_step(eps, x, hist, noise, x_in, t_in, t_next, coef):
+    """One scheduler step in one launch (include/clora.h clora_sampler_step_f16): the guidance combine of `eps` (fp16 [2B,C,H,W], uncond
+    half first, ANY non-zero element strides -- dense NCHW or the permuted NHWC view the UNet returns), the update of the fp32 state
+    `x` [B,C,H,W] in place, this step's x0 into `hist` (fp32 like x, or None; read only when k_h != 0), `noise` (fp32 like x, or None
+    when k_n == 0), the fp16 of the new state into both halves of `x_in` ([2B,C,H,W] or None) and `t_next` into `t_in` (int64 [1] or
+    None).  `coef`: the eight numbers (guidance, x0_x, x0_e, k_x, k_x0, k_h, k_e, k_n) as a mapping or a sequence in that order
+    (schedulers `coefficients`); they go by value, rounded to fp32."""
+    if x.dim() != 4 or eps.dim() != 4:
+        raise capi.CloraError(f"sampler_step: eps {tuple(eps.shape)} and x {tuple(x.shape)} must be [2B,C,H,W] and [B,C,H,W]")
+    B, Cc, H, W = x.shape
+    if tuple(eps.shape) != (2 * B, Cc, H, W):
+        raise capi.CloraError(f"sampler_step: eps {tuple(eps.shape)} is not the CFG batch [2B,C,H,W] of x {tuple(x.shape)}")
+    for name, t, dt, shape in (("x", x, f32, (B, Cc, H, W)), ("hist", hist, f32, (B, Cc, H, W)), ("noise", noise, f32, (B, Cc, H, W)),
+                               ("x_in", x_in, f16, (2 * B, Cc, H, W)), ("t_in", t_in, torch.int64, (1,))):
+        if t is None:
+            continue
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != eps.device:
+            raise capi.CloraError(f"sampler_step: {name} must be a dense {dt} tensor of shape {shape} on {eps.device}, got {t.dtype} "
+                                  f"{tuple(t.shape)} strides {t.stride()} on {t.device}")
+    vals = [coef[n] for n in SAMPLER_COEF_NAMES] if hasattr(coef, "keys") else list(coef)
+    if len(vals) != len(SAMPLER_COEF_NAMES):
+        raise capi.CloraError(f"sampler_step: {len(vals)} coefficients, expected {SAMPLER_COEF_NAMES}")
+    k = capi.SamplerCoef(*(float(v) for v in vals))
+    moved = 2 * eps.numel() + 8 * x.numel() + sum(t.numel() * t.element_size() for t in (hist, noise, x_in) if t is not None)
+    _call("clora_sampler_step_f16", ptr(eps, f16), *(int(s) for s in eps.stride()), ptr(x, f32), ptr(hist), ptr(noise), ptr(x_in),
+          ptr(t_in), int(t_next), B, Cc, H, W, C.byref(k), nbytes=float(moved))
+
+
 def grad_sumsq(g, state):
     _call("clora_grad_sumsq_f32", ptr(g, f32), g.numel(), ptr(state, f32))
 

@@ -11,7 +11,8 @@ from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler
 
 @torch.no_grad()
 def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guidance_scale=9.0, latents=None,
-                generator=None, sampler="ddim", graph=None, cache_text_kv=True, callback=None, size=None):
+                generator=None, sampler="ddim", graph=None, cache_text_kv=True, callback=None, size=None, eta=0.0, noise=None,
+                step_impl="host"):
     """guide [Bc,3,H,W] (control batch 1 broadcasts over the CFG batch, quirk C6); cond/uncond [B,77,768].
     control_lora / guide may be equal-length lists: the main model (whose processors sit on the UNet) first, then the models
     chained onto it with models.mix_control_loras, each with the guide it reads.
@@ -25,8 +26,20 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
     callback(i, latents, eps): called after scheduler step i = 1..steps (tests record the trajectory with it).
     Without a control model (`control_lora=None`, plain text-to-image) `guide` may be None: `size` = (height, width) of the image
     in pixels, or `latents`, then gives the latent size.
+    eta: DDIM's stochastic family (0: deterministic, 1: the DDPM variance).  With eta > 0 step i takes `noise[i - 1]` when `noise`
+    ([steps,B,4,H,W], standard normal) is given, else one `torch.randn(..., generator=generator)` draw per step.  With
+    sampler="dpm" eta is ignored, as in the reference (its DPM-Solver++ scheduler has no such parameter).
+    step_impl: "host" -- the guidance combine and the scheduler update are torch ops on the latents (schedulers `step`);
+    "device" -- after each UNet evaluation, eager or replayed, ONE kernels.sampler_step launch on the current stream does both and
+    writes the next UNet input and timestep; the coefficients go by value (schedulers `coefficients`).  On the device path the
+    callback's `latents` is the in-place state, valid until the next step.
     Returns the denoised latents in **fp32** (the scheduler state is kept in fp32 between steps)."""
     from . import models
+    if step_impl not in ("host", "device"):
+        raise ValueError(f"step_impl {step_impl!r}: expected 'host' or 'device'")
+    if sampler != "ddim":
+        eta = 0.0
+    eta = float(eta)
     B = cond_emb.shape[0]
     dev = cond_emb.device
     # several control models steering one image (models.mix_control_loras): equal-length lists, the main model first
@@ -78,12 +91,25 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
     if graph is None:
         # capture costs one extra warm-up forward + the capture itself: only worth it for real sampling runs
         graph = dev.type == "cuda" and steps >= 8
+    if noise is not None and eta and tuple(noise.shape) != (steps, B, 4, H, W):
+        raise ValueError(f"noise {tuple(noise.shape)}: expected one standard-normal tensor per step, {(steps, B, 4, H, W)}")
+
+    def step_noise(i):                                   # the noise of step i = 1..steps: None unless eta > 0
+        if not eta:
+            return None
+        if noise is not None:
+            return noise[i - 1].to(device=dev, dtype=torch.float32).contiguous()
+        return torch.randn((B, 4, H, W), device=dev, dtype=torch.float32, generator=generator)
+
+    step_kw = (lambda i: dict(eta=eta, noise=step_noise(i))) if eta else (lambda i: {})
     with models.text_kv_cache(enabled=cache_text_kv):
+        if step_impl == "device":
+            return _device_steps(unet, sched, ehs, latents, guidance_scale, eta, step_noise, graph, callback)
         if not graph:
             for i, t in enumerate(sched.timesteps, 1):
                 eps = unet(torch.cat([latents, latents], 0).half(), t, ehs).sample
                 eps_u, eps_c = eps.float().chunk(2)
-                latents = sched.step(eps_u + guidance_scale * (eps_c - eps_u), t, latents)
+                latents = sched.step(eps_u + guidance_scale * (eps_c - eps_u), t, latents, **step_kw(i))
                 if callback is not None:
                     callback(i, latents, eps)
             return latents
@@ -104,10 +130,45 @@ def ddim_sample(unet, control_lora, guide, cond_emb, uncond_emb, steps=50, guida
             t_in.fill_(int(t))
             g.replay()
             eps_u, eps_c = eps_out.float().chunk(2)
-            latents = sched.step(eps_u + guidance_scale * (eps_c - eps_u), t, latents)
+            latents = sched.step(eps_u + guidance_scale * (eps_c - eps_u), t, latents, **step_kw(i))
             if callback is not None:
                 callback(i, latents, eps_out)
         return latents
+
+
+def _device_steps(unet, sched, ehs, latents, guidance_scale, eta, step_noise, graph, callback):
+    """The loop of ddim_sample(step_impl="device"): the fp32 state `x`, the previous x0 `hist` (DPM-Solver++ only), the UNet input
+    `x_in` and its timestep `t_in` live on the device; one kernels.sampler_step launch per step updates all four."""
+    from . import kernels as K
+    dev = latents.device
+    B = latents.shape[0]
+    ddim = isinstance(sched, DDIMScheduler)
+    ts = list(sched.timesteps)
+    x = latents.float().contiguous().clone()             # updated in place: never the caller's tensor
+    hist = None if ddim else torch.zeros_like(x)
+    x_in = torch.cat([x, x], 0).half()
+    t_in = torch.full((1,), int(ts[0]), device=dev, dtype=torch.long)
+    g = None
+    if graph:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                # warm-up outside the capture: lazy weight packs, K/V cache, allocator
+            unet(x_in, t_in, ehs)
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            eps = unet(x_in, t_in, ehs).sample
+    for i, t in enumerate(ts, 1):
+        coef = sched.coefficients(i - 1, guidance_scale, eta) if ddim else sched.coefficients(i - 1, guidance_scale)
+        nz = step_noise(i)
+        if g is not None:
+            g.replay()
+        else:
+            eps = unet(x_in, t_in, ehs).sample
+        K.sampler_step(eps, x, hist, nz, x_in, t_in, ts[i] if i < len(ts) else 0, coef)
+        if callback is not None:
+            callback(i, x, eps)
+    return x
 
 
 class ControlLoRAPipeline:
@@ -155,12 +216,13 @@ class ControlLoRAPipeline:
 
     @torch.no_grad()
     def __call__(self, prompt, guide=None, a_prompt="", n_prompt="", num_samples=1, ddim_steps=50, scale=9.0, seed=None,
-                 output_type="uint8", sampler="ddim", height=None, width=None):
+                 output_type="uint8", sampler="ddim", height=None, width=None, eta=0.0, step_impl="host"):
         """guide: float tensor [1, 3, H, W] (broadcast over the samples) or [num_samples, 3, H, W] (one guide per image), in
         [-1, 1]; H, W multiples of 64, square or not -- every size the reference apps' image_resolution slider gives (256 ... 768):
         the UNet's and the VAE's attention are flash kernels that take any number of tokens.  A pipeline built from a list of control
         models ([main, member, ...]) takes a list of guides, one per model in that order, all of one size.
-        A pipeline without a control model takes no guide: `height` / `width` (multiples of 64, default 512) size the image."""
+        A pipeline without a control model takes no guide: `height` / `width` (multiples of 64, default 512) size the image.
+        eta / step_impl: see ddim_sample (eta is DDIM's; step_impl "device" runs each scheduler step as one launch)."""
         if guide is None:
             if self.control_lora is not None:
                 raise ValueError("this pipeline has a control model: it needs a guide image")
@@ -181,7 +243,7 @@ class ControlLoRAPipeline:
                 guide = [guide]                        # (a list of one model takes a bare guide too)
         lat = ddim_sample(self.unet, self.control_lora, guide, cond, uncond,
                           steps=ddim_steps, guidance_scale=scale, generator=gen, sampler=sampler,
-                          size=None if guide is not None else (height, width))
+                          size=None if guide is not None else (height, width), eta=eta, step_impl=step_impl)
         img = self.vae.decode(lat.half() / self.vae.scaling_factor).sample.float().clamp(-1, 1)
         if output_type == "uint8":
             return ((img.permute(0, 2, 3, 1) + 1.0) * 127.5).round().to(torch.uint8).cpu()

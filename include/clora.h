@@ -723,6 +723,32 @@ int clora_canny_hysteresis_u8(uint8_t* state, unsigned* flags, int pass_base, in
  *   three channels equal -- what the data set's `edges / 127.5 - 1` gives, in the layout the hint encoder takes. */
 int clora_canny_emit(const uint8_t* state, uint8_t* edges, clora_half* guide, int B, int H, int W, void* stream);
 
+/* ---- one scheduler step of the sampling loop in one launch (controllora_amd/pipeline.py `step_impl="device"`): the classifier-free
+ * guidance combine, the sampler update of the fp32 state and the next UNet input.  Per element, all in fp32:
+ *     e  = eps_u + guidance * (eps_c - eps_u)
+ *     x0 = x0_x * x + x0_e * e
+ *     x' = k_x * x + k_x0 * x0 + k_h * hist + k_e * e + k_n * noise
+ * DDIM with any eta and DPM-Solver++ of first and second order (2M) are coefficient sets of this form (INTEGRATION.md "Sampler step";
+ * controllora_amd/schedulers.py `coefficients`).
+ *   eps    fp16, 2B samples addressed by ELEMENT strides es_n / es_c / es_h / es_w (all non-zero): samples 0 .. B-1 are the
+ *          unconditional half, B .. 2B-1 the conditional one.  A dense NCHW tensor and the view the UNet returns (NHWC rows of the
+ *          padded conv_out width, es_c = 1) both coalesce; C = 4 with es_c = 1 and 8-byte aligned pixels is one load per pixel.
+ *   x      fp32 dense NCHW [B,C,H,W], updated in place.
+ *   hist   fp32 like x, or NULL: read only when k_h != 0, ALWAYS overwritten with this step's x0 (the history of the 2M update).
+ *   noise  fp32 like x, or NULL: never read when k_n == 0; NULL with k_n != 0 is CLORA_ERR_ARG.
+ *   x_in   fp16 dense [2B,C,H,W], or NULL: both halves receive the round-to-nearest-even fp16 of the x' that was stored.
+ *   t_in   NULL, or device int64[1] that receives t_next.
+ *   coef   HOST memory, read at the call.
+ * NULL eps / x / coef, B, C, H or W below 1, a zero stride: CLORA_ERR_ARG, nothing launched.  No atomics, no workspace, no host
+ * synchronisation; every element is produced by one thread in a fixed order of operations, so the result does not depend on the
+ * grid and repeat launches are bit-identical.  Against the fp64 form: |x' - ref| <= 12 * 2^-24 * S with S the sum of the absolute
+ * values of the terms (tests/sampler_step_cases.py). */
+typedef struct { float guidance, x0_x, x0_e, k_x, k_x0, k_h, k_e, k_n; } clora_sampler_coef_t;
+int clora_sampler_step_f16(const clora_half* eps, long long es_n, long long es_c, long long es_h, long long es_w,
+                           float* x, float* hist, const float* noise, clora_half* x_in,
+                           long long* t_in, long long t_next,
+                           int B, int C, int H, int W, const clora_sampler_coef_t* coef, void* stream);
+
 /* Box calibration (bench.py "calibration"): `blocks` workgroups of 4 waves issue iters x 8 independent dense MFMAs each on
  * pseudo-random operands; out[3b .. 3b+2] = {shader cycles, 100 MHz wall ticks, checksum} of block b.  No reference
  * counterpart: it exists so that a bench line can be normalised by the clock the box actually held (DVFS). */
