@@ -9,7 +9,8 @@ with `inject_pre_lora` (reference models.py:232-243); here the chained members a
         --input photo.png --prompt "a dancer" --out out.png
 
 `--control_lora DIR` and `--guide PATH` come in pairs, the main model first.  `--guide canny` makes that guide from `--input` with the
-canny app's detector options; any other value is an image file used as it is (resized to the generated size).  The output is
+canny app's detector options, `--guide openpose` runs the OpenPose body detector (`--openpose PATH|random:openpose`) on it as the pose
+app does; any other value is an image file used as it is (resized to the generated size).  The output is
 [guide_0 | guide_1 | ... | images].  `--no_fold` keeps the chained members on the unfused path.
 """
 from __future__ import annotations
@@ -27,7 +28,7 @@ sys.path.insert(0, os.path.abspath(os.path.dirname(__file__)))
 from canny2image import detect, hwc3, resize_image          # noqa: E402
 
 
-def load_guides(specs, input_image, image_resolution, low, high, detector):
+def load_guides(specs, input_image, image_resolution, low, high, detector, openpose=None, detect_resolution=512):
     """-> (uint8 [H,W,3] maps as shown in the output strip, float control tensors [1,3,H,W] in [-1, 1]), all of one size"""
     import torch
     from PIL import Image
@@ -40,6 +41,13 @@ def load_guides(specs, input_image, image_resolution, low, high, detector):
                 raise SystemExit("--guide canny needs --input")
             detected = hwc3(detect(base, low, high, detector))
             shown.append(255 - detected)
+        elif spec == "openpose":
+            if input_image is None or openpose is None:
+                raise SystemExit("--guide openpose needs --input and --openpose")
+            from pose2image import nearest_resize
+            pose_map, _ = openpose(resize_image(hwc3(input_image), detect_resolution))       # reference apps/gradio_pose2image.py:75-77
+            detected = nearest_resize(hwc3(pose_map), base.shape[1], base.shape[0])
+            shown.append(detected)
         else:
             img = hwc3(np.asarray(Image.open(spec).convert("RGB")))
             if size is None:
@@ -62,8 +70,10 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--base", required=True, help="SD-1.5 checkpoint directory (diffusers layout) or random:sd15 / random:sd15-small")
     ap.add_argument("--control_lora", action="append", required=True, help="directory written by ControlLoRA.save_pretrained; repeat, main model first")
-    ap.add_argument("--guide", action="append", required=True, help="'canny' (made from --input) or an image file; one per --control_lora, same order")
-    ap.add_argument("--input", default=None, help="the image `--guide canny` reads")
+    ap.add_argument("--guide", action="append", required=True, help="'canny' or 'openpose' (made from --input) or an image file; one per --control_lora, same order")
+    ap.add_argument("--input", default=None, help="the image `--guide canny` / `--guide openpose` read")
+    ap.add_argument("--openpose", default=None, metavar="PATH|random:openpose", help="body_pose_model.pth for `--guide openpose`")
+    ap.add_argument("--detect_resolution", type=int, default=512, help="short side of the OpenPose detector's input")
     ap.add_argument("--prompt", required=True)
     ap.add_argument("--a_prompt", default="best quality, extremely detailed")
     ap.add_argument("--n_prompt", default="longbody, lowres, bad anatomy, bad hands, missing fingers, extra digit, fewer digits, cropped, worst quality, low quality")
@@ -89,7 +99,13 @@ def main(argv=None):
     from controllora_amd.pipeline import ControlLoRAPipeline
     pipe = ControlLoRAPipeline.from_pretrained(a.base, list(a.control_lora), fold=not a.no_fold)
     inp = np.asarray(Image.open(a.input).convert("RGB")) if a.input else None
-    shown, controls = load_guides(a.guide, inp, a.image_resolution, a.low_threshold, a.high_threshold, a.detector)
+    openpose = None
+    if "openpose" in a.guide:
+        if not a.openpose:
+            raise SystemExit("--guide openpose needs --openpose PATH|random:openpose")
+        from controllora_amd.openpose import OpenposeDetector
+        openpose = OpenposeDetector(a.openpose)
+    shown, controls = load_guides(a.guide, inp, a.image_resolution, a.low_threshold, a.high_threshold, a.detector, openpose, a.detect_resolution)
     results = process(pipe, shown, controls, a.prompt, a.a_prompt, a.n_prompt, a.num_samples, a.sample_steps, a.scale, a.seed, a.sampler,
                       a.sampler_step)
     with torch.no_grad():

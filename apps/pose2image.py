@@ -1,14 +1,16 @@
 #!/usr/bin/env python
 """Command-line form of the pose app's `process()` (reference apps/gradio_pose2image.py:68-96) on the MI355X path.
 
-The reference runs an OpenPose annotator on the input photo (out of scope here: SURVEY.md section 2 marks `annotator/` OOS);
-what it does WITH the detected map is the call pattern this file keeps: the pose map (a pre-rendered skeleton image -- the
-`--pose` argument, e.g. the first image the reference app returns) is resized to the generation resolution with NEAREST
+The reference runs its OpenPose annotator on the input photo (line 75: `apply_openpose(resize_image(input_image, detect_resolution))`);
+so does this file with `--input photo --openpose PATH|random:openpose` (controllora_amd/openpose.py, body model on the HIP kernels), or
+it takes a pre-rendered skeleton image with `--pose`.  Either way the pose map is resized to the generation resolution with NEAREST
 interpolation (`cv2.resize(..., INTER_NEAREST)`, line 77), turned into the control tensor `map[..., ::-1] / 127.5 - 1`
 (line 79), hint-encoded once per sample, and sampled with CFG -- 30 DPM-Solver++ steps by default (slider default, line 112).
 
     python apps/pose2image.py --base /path/to/stable-diffusion-v1-5 --control_lora /path/to/sd-mpii-pose-model-control-lora \\
         --pose skeleton.png --prompt "a man dancing" --out out.png --num_samples 2 --image_resolution 512
+    python apps/pose2image.py --base random:sd15 --control_lora /path/to/sd-mpii-pose-model-control-lora \\
+        --openpose /path/to/body_pose_model.pth --input photo.png --prompt "a man dancing" --out out.png
 
 `process()` keeps the reference's argument list (the `input_image` slot carries the photo that only fixes the output size; pass
 the pose map itself when there is no photo) and its return convention ([detected map] + generated images, uint8 HWC).
@@ -37,13 +39,17 @@ def nearest_resize(img: np.ndarray, W: int, H: int) -> np.ndarray:
 
 
 def process(pipe, input_image, prompt, a_prompt, n_prompt, num_samples, image_resolution, detect_resolution, sample_steps, scale,
-            seed, eta, pose_map=None, sampler="dpm", sampler_step="host"):
-    """reference argument order (apps/gradio_pose2image.py:68) + `pose_map`: the annotator's output, supplied instead of computed
-    (None: `input_image` IS the pose map).  `detect_resolution` only sized the annotator's input in the reference and is accepted
-    for compatibility.  `eta` is DDIM's (0: deterministic; DPM-Solver++ has no such parameter and ignores it); `sampler_step="device"`
+            seed, eta, pose_map=None, sampler="dpm", sampler_step="host", detector=None):
+    """reference argument order (apps/gradio_pose2image.py:68) + `pose_map`: the annotator's output, supplied instead of computed,
+    or `detector`: an `OpenposeDetector` that computes it as the reference does (line 75), on `resize_image(input_image,
+    detect_resolution)`.  Neither: `input_image` IS the pose map.  `eta` is DDIM's (0: deterministic; DPM-Solver++ has no such parameter and ignores it); `sampler_step="device"`
     runs each scheduler step as one launch (controllora_amd.kernels.sampler_step)."""
     import torch
+    if pose_map is not None and detector is not None:
+        raise ValueError("pose_map and detector are alternatives")
     input_image = hwc3(input_image)
+    if detector is not None:
+        pose_map, _ = detector(resize_image(input_image, detect_resolution))
     detected_map = hwc3(pose_map if pose_map is not None else resize_image(input_image, detect_resolution))
     img = resize_image(input_image, image_resolution)
     H, W, _ = img.shape
@@ -60,8 +66,10 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--base", required=True, help="SD-1.5 checkpoint directory (diffusers layout) or random:sd15")
     ap.add_argument("--control_lora", required=True, help="directory written by ControlLoRA.save_pretrained")
-    ap.add_argument("--pose", required=True, help="pre-rendered pose map (the OpenPose annotator is out of scope)")
-    ap.add_argument("--input", default=None, help="optional photo: only fixes the aspect ratio of the output, like the reference")
+    ap.add_argument("--pose", default=None, help="pre-rendered pose map; without it the detector runs on --input")
+    ap.add_argument("--openpose", default=None, metavar="PATH|random:openpose",
+                    help="body_pose_model.pth (or random:openpose, seeded random weights) for the OpenPose body detector")
+    ap.add_argument("--input", default=None, help="photo: the detector's input; with --pose it only fixes the aspect ratio of the output")
     ap.add_argument("--prompt", required=True)
     ap.add_argument("--a_prompt", default="best quality, extremely detailed")
     ap.add_argument("--n_prompt", default="longbody, lowres, bad anatomy, bad hands, missing fingers, extra digit, fewer digits, cropped, worst quality, low quality")
@@ -78,13 +86,21 @@ def main(argv=None):
                     help="scheduler step as torch ops on the latents (host) or as one HIP launch per step (device)")
     ap.add_argument("--out", default="pose2image.png")
     a = ap.parse_args(argv)
+    if a.pose is None and not (a.input and a.openpose):
+        ap.error("give --pose MAP, or --input PHOTO with --openpose WEIGHTS")
+    if a.pose is not None and a.openpose:
+        ap.error("--pose and --openpose are alternatives")
     from PIL import Image
     from controllora_amd.pipeline import ControlLoRAPipeline
     pipe = ControlLoRAPipeline.from_pretrained(a.base, a.control_lora)
-    pose = np.asarray(Image.open(a.pose).convert("RGB"))
+    pose = np.asarray(Image.open(a.pose).convert("RGB")) if a.pose else None
     photo = np.asarray(Image.open(a.input).convert("RGB")) if a.input else pose
+    detector = None
+    if pose is None:
+        from controllora_amd.openpose import OpenposeDetector
+        detector = OpenposeDetector(a.openpose)
     results = process(pipe, photo, a.prompt, a.a_prompt, a.n_prompt, a.num_samples, a.image_resolution, a.detect_resolution,
-                      a.sample_steps, a.scale, a.seed, a.eta, pose_map=pose, sampler=a.sampler, sampler_step=a.sampler_step)
+                      a.sample_steps, a.scale, a.seed, a.eta, pose_map=pose, sampler=a.sampler, sampler_step=a.sampler_step, detector=detector)
     Image.fromarray(np.concatenate(results, axis=1)).save(a.out)
     print("wrote", a.out)
 

@@ -157,6 +157,13 @@ class SamplerCoef(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("guidance", "x0_x", "x0_e", "k_x", "k_x0", "k_h", "k_e", "k_n")]
 
 
+class ConvActJob(C.Structure):
+    """mirror of clora_conv_act_job_t"""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldy", C.c_int),
+                ("Cin", C.c_int), ("Cout", C.c_int), ("relu", C.c_int)]
+
+
+CONV_ACT_MAX_JOBS = 2          # CLORA_CONV_ACT_MAX_JOBS
 LORA_MAX_JOBS = 16
 LORA_WGRAD_MAX_JOBS = 32       # CLORA_LORA_WGRAD_MAX_JOBS
 WGRAD_JOBS_PER_LAUNCH = min(LORA_WGRAD_MAX_JOBS, max(1, int(os.environ.get("CLORA_WGRAD_JOBS", "32"))))   # A/B runs: 16 = the round-5 batching
@@ -236,6 +243,11 @@ _PROTOS = {
     "clora_canny_hysteresis_u8": [_P, _P, _I, _I, _I, _I, _I, _P],
     "clora_canny_emit": [_P, _P, _P, _I, _I, _I, _P],
     "clora_sampler_step_f16": [_P, _LL, _LL, _LL, _LL, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, C.POINTER(SamplerCoef), _P],
+    "clora_conv_act_f16": [C.POINTER(ConvActJob), _I, _I, _I, _I, _I, _P, _Z, _P],
+    "clora_conv_act_workspace": [C.POINTER(ConvActJob), _I, _I, _I, _I, _I],
+    "clora_conv_act_splits": [C.POINTER(ConvActJob), _I, _I, _I, _I, _I],
+    "clora_conv_act_pack_f32": [_P, _P, _P, _I, _I, _I, _I, _P],
+    "clora_maxpool2x2_f16": [_P, _P, _I, _I, _I, _I, _P],
     "clora_abi_version": [],
     "clora_clock_probe": [_P, _I, _I, _P],
     "clora_groupnorm_workspace_bytes": [_I, _I, _I, _I, _I, _I],
@@ -273,6 +285,8 @@ class Lib:
         self.cdll.clora_groupnorm_team_state_bytes.restype = C.c_size_t
         self.cdll.clora_lora_wgrad_workspace_bytes.restype = C.c_size_t
         self.cdll.clora_rank_gram_ws_bytes.restype = C.c_size_t
+        if hasattr(self.cdll, "clora_conv_act_workspace"):
+            self.cdll.clora_conv_act_workspace.restype = C.c_size_t
         self._options_from_env()
         self._derived = {}
 

@@ -1195,3 +1195,69 @@ def canny(img_u8: torch.Tensor, low, high, guide: bool = False, stats: Optional[
     if stats is not None:
         stats["launches"] += 1                                 # the classify launch
     return out[0] if (single and not guide) else out
+
+
+# ------------------------------------------------------------------ OpenPose body network (controllora_amd/openpose.py)
+def conv_act_packed_numel(Cout: int, Cin: int, ksize: int) -> int:
+    """elements of the weight operand of `conv_act` (include/clora.h clora_conv_act_pack_f32): [k * k][Cin32 / 8][CoutP][8]"""
+    return ksize * ksize * ((Cin + 31) // 32 * 32) * ((Cout + 15) // 16 * 16)
+
+
+def conv_act_pack(w: torch.Tensor, Cin: Optional[int] = None, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 OIHW weights [Cout, CinSrc, k, k] -> the fp16 operand of `conv_act` for `Cin` kernel-side input channels (a multiple of 8,
+    default CinSrc rounded up to 8); `perm`: int32 [Cin] on the weights' device, the source channel of every kernel-side channel
+    (-1: a pad channel, weights zero), default the identity with zero pad."""
+    assert w.dim() == 4 and w.dtype == f32 and w.is_contiguous() and w.shape[2] == w.shape[3], "fp32 OIHW"
+    Cout, CinSrc, k, _ = w.shape
+    Cin = (CinSrc + 7) // 8 * 8 if Cin is None else int(Cin)
+    if perm is not None:
+        assert perm.dtype == torch.int32 and perm.shape == (Cin,) and perm.is_contiguous() and perm.device == w.device
+    out = torch.empty(conv_act_packed_numel(Cout, Cin, k), dtype=f16, device=w.device)
+    _call("clora_conv_act_pack_f32", ptr(w, f32), ptr(out), ptr(perm), Cout, CinSrc, Cin, k)
+    return out
+
+
+def _conv_act_jobs(jobs, rows):
+    arr = (capi.ConvActJob * len(jobs))()
+    for i, j in enumerate(jobs):
+        x, y = j["x"], j["y"]
+        assert x.dtype == f16 and y.dtype == f16 and x.dim() == 2 and y.dim() == 2 and x.stride(1) == 1 and y.stride(1) == 1, "fp16 [rows, C] views"
+        assert x.shape[0] == rows and y.shape[0] == rows and y.shape[1] == j["Cout"] and x.shape[1] == j["Cin"]
+        assert j["w"].numel() == conv_act_packed_numel(j["Cout"], j["Cin"], j["ksize"]) and j["bias"].numel() == j["Cout"]
+        arr[i] = capi.ConvActJob(ptr(x), x.stride(0), ptr(j["w"], f16), ptr(j["bias"], f32), ptr(y), y.stride(0), j["Cin"], j["Cout"],
+                                 int(bool(j["relu"])))
+    return arr
+
+
+def conv_act_splits(jobs, B, H, W, ksize) -> int:
+    """the number of K ranges `conv_act` cuts these jobs into (1: one direct launch; more: slabs + a finish launch)"""
+    arr = _conv_act_jobs([dict(j, ksize=ksize) for j in jobs], B * H * W)
+    n = capi.lib().cdll.clora_conv_act_splits(arr, len(jobs), B, H, W, ksize)
+    if n < 1:
+        raise capi.CloraError(f"clora_conv_act_splits failed: {n}")
+    return n
+
+
+def conv_act(jobs, B: int, H: int, W: int, ksize: int) -> int:
+    """One launch (plus a finish launch where K is split) for up to two stride-1 "same" convolutions of the same B, H, W, ksize with a
+    fused bias and optional ReLU (include/clora.h clora_conv_act_f16).  A job is a dict: x fp16 [B*H*W, Cin] view (row stride >= Cin),
+    w (from `conv_act_pack`), bias fp32 [Cout], y fp16 [B*H*W, Cout] view into the output buffer (an even channel offset), Cin, Cout,
+    relu.  Exactly y's Cout columns are written.  -> the number of launches."""
+    rows = B * H * W
+    arr = _conv_act_jobs([dict(j, ksize=ksize) for j in jobs], rows)
+    L = capi.lib()
+    need = int(L.cdll.clora_conv_act_workspace(arr, len(jobs), B, H, W, ksize))
+    ws = workspace(need, jobs[0]["x"].device) if need else None
+    flops = sum(2.0 * rows * j["Cout"] * j["Cin"] * ksize * ksize for j in jobs)
+    _call("clora_conv_act_f16", arr, len(jobs), B, H, W, ksize, ptr(ws), ws.numel() if ws is not None else 0, flops=flops)
+    return 2 if need else 1
+
+
+def maxpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp16 NHWC [B, H, W, C] (dense, H and W even, C % 8 == 0) -> [B, H/2, W/2, C], F.max_pool2d(kernel 2, stride 2) bit for bit"""
+    assert x.dim() == 4 and x.dtype == f16 and x.is_contiguous(), "fp16 NHWC [B,H,W,C]"
+    B, H, W, Cc = x.shape
+    y = out if out is not None else torch.empty((B, H // 2, W // 2, Cc), dtype=f16, device=x.device)
+    assert y.dtype == f16 and y.is_contiguous() and y.numel() == B * (H // 2) * (W // 2) * Cc
+    _call("clora_maxpool2x2_f16", ptr(x), ptr(y), B, H, W, Cc, nbytes=2.0 * (x.numel() + y.numel()))
+    return y

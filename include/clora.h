@@ -749,6 +749,44 @@ int clora_sampler_step_f16(const clora_half* eps, long long es_n, long long es_c
                            long long* t_in, long long t_next,
                            int B, int C, int H, int W, const clora_sampler_coef_t* coef, void* stream);
 
+/* ---- the OpenPose body network (controllora_amd/openpose.py; reference annotator/openpose/model.py `bodypose_model`, run by the pose
+ * app, reference apps/gradio_pose2image.py:75): stride-1 "same" convolutions with a fused bias / ReLU, a 2x2 max pool, a weight pack.
+ *
+ * conv_act: y[b, h, w, 0 .. Cout) = act(sum_{ky, kx, ci} x[b, h + ky - k/2, w + kx - k/2, ci] * W[co, ci, ky, kx] + bias[co]), zero
+ *   outside the map; ksize 1, 3 or 7; fp16 NHWC rows (x: row pitch ldx >= Cin, 16-byte aligned, ldx % 8 == 0; y: row pitch ldy, even,
+ *   the pointer 4-byte aligned -- i.e. an EVEN channel offset into a wider buffer), fp32 accumulation on the matrix cores, fp32 bias
+ *   [Cout], relu != 0: max(., 0) before the fp16 rounding.  Exactly the channels 0 .. Cout - 1 of every row of y are written, nothing
+ *   else of the row: the branch heads of a stage (Cout 38 and 19) store into the 192-channel stage buffer beside the trunk features.
+ *   `jobs` is a HOST array of 1 .. CLORA_CONV_ACT_MAX_JOBS convolutions of the same B, H, W, ksize (the L1 and L2 branch of a stage),
+ *   read at the call; they run in ONE launch.  Cin % 8 == 0 (the caller pads: image 3 -> 8, concatenation 185 -> 192); w is the
+ *   operand the pack entry point below writes for (Cout, Cin, ksize).
+ *   Launch shape: 8 x 8 pixel tiles x 64-channel tiles x jobs; where that is fewer workgroups than the device has CUs, K is cut over
+ *   (32-channel slab, kernel row) units into `splits` ranges whose fp32 sums go to slabs in `workspace` and a finish launch adds them in
+ *   a fixed order (no atomics: two calls on the same input give the same bits).  The workspace entry point returns the bytes that takes
+ *   (0: direct), the splits one the number of ranges (1: direct) or CLORA_ERR_ARG; both are functions of the shapes alone.
+ *   njobs outside 1 .. 2, ksize outside {1, 3, 7}, Cin % 8 != 0, a misaligned pointer / odd channel offset or pitch: CLORA_ERR_ARG, nothing
+ *   launched; a missing or short workspace: CLORA_ERR_WORKSPACE. */
+#define CLORA_CONV_ACT_MAX_JOBS 2
+typedef struct {
+    const clora_half* x; int ldx;
+    const clora_half* w;
+    const float* bias;
+    clora_half* y; int ldy;
+    int Cin, Cout, relu;
+} clora_conv_act_job_t;
+int clora_conv_act_f16(const clora_conv_act_job_t* jobs, int njobs, int B, int H, int W, int ksize, void* workspace,
+                       size_t workspace_bytes, void* stream);
+size_t clora_conv_act_workspace(const clora_conv_act_job_t* jobs, int njobs, int B, int H, int W, int ksize);
+int clora_conv_act_splits(const clora_conv_act_job_t* jobs, int njobs, int B, int H, int W, int ksize);
+/* pack: w fp32 OIHW [Cout, CinSrc, k, k] -> out fp16 [k * k][Cin32 / 8][CoutP][8], Cin32 = CinDst rounded up to 32, CoutP = Cout rounded
+ *   up to 16: out[tap][c / 8][co][c % 8] = W[co, perm[c], tap] -- zero where c >= CinDst, perm[c] < 0 or >= CinSrc, or co >= Cout.
+ *   perm: DEVICE int [CinDst] (the source channel of every kernel-side channel, -1 = a pad channel) or NULL for the identity.
+ *   One launch per layer, at load time. */
+int clora_conv_act_pack_f32(const float* w, clora_half* out, const int* perm, int Cout, int CinSrc, int CinDst, int ksize, void* stream);
+/* max pool, kernel 2 stride 2: x fp16 NHWC [B, H, W, C] dense -> y [B, H/2, W/2, C]; H and W even, C % 8 == 0, 16-byte aligned
+ *   (else CLORA_ERR_ARG); the values F.max_pool2d gives, bit for bit */
+int clora_maxpool2x2_f16(const clora_half* x, clora_half* y, int B, int H, int W, int C, void* stream);
+
 /* Box calibration (bench.py "calibration"): `blocks` workgroups of 4 waves issue iters x 8 independent dense MFMAs each on
  * pseudo-random operands; out[3b .. 3b+2] = {shader cycles, 100 MHz wall ticks, checksum} of block b.  No reference
  * counterpart: it exists so that a bench line can be normalised by the clock the box actually held (DVFS). */
